@@ -7,6 +7,11 @@ on one GPU both run in one C call (pcg_pc_skeleton, stream-ordered, no host roun
 N=1: one GPU. N>1 (torchrun): the same skeleton edge-sharded across ranks, removal flags
 merged with an RCCL all-reduce at every level barrier (strong scaling of one fixed graph).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs DIR is given, and prints the line. --full adds, after the timed steps, what the
+headline figure does not need: K1 alone (for its roofline), the full-p comparison run and the
+CPU baseline with its parity check.
 """
 from __future__ import annotations
 
@@ -228,8 +233,16 @@ def parse():
     ap.add_argument("--alpha", type=float, default=0.05)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--full-p", action="store_true", help="compute every p-value (PCG_FLAG_FULL_P)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-full-p", action="store_true", help="skip the full-p comparison run after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: K1 alone for its "
+                         "roofline, the full-p comparison run and the CPU baseline with its parity check "
+                         "(a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-full-p", action="store_true",
+                    help="with --full: skip the full-p comparison run after the timed steps")
     ap.add_argument("--cpu-depth", type=int, default=3, help="depths timed for the CPU port baseline")
     ap.add_argument("--json-extra", action="store_true", help="print per-level detail to stderr")
     ap.add_argument("--workload", choices=["skeleton", "rq2"], default="skeleton",
@@ -309,6 +322,62 @@ def cpu_reference_equiv(X: np.ndarray, ref, budget_s: float = 4.0) -> dict:
             count += 1
     dt = time.perf_counter() - t0
     return {"value": count / dt, "cores": 1, "tests": count, "seconds": dt}
+
+
+DUMP_SEED = 12345
+# byte budget of each dumped array (60 MB in all); a larger one is cut to a fixed, seeded sample of its rows
+DUMP_BUDGET = {"corr": 32_000_000, "removed_level": 16_000_000, "sep": 11_000_000, "small": 500_000}
+
+
+def _dump_rows(rows: int, row_bytes: int, budget: int):
+    """Sorted, seeded row indices of an array of ``rows`` rows that fit ``budget`` bytes; None = every row."""
+    keep = budget // max(row_bytes, 1)
+    if rows <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+
+
+def dump_outputs(path: str, out, C) -> dict:
+    """Write what the last timed step returned (the SkeletonOut a caller of the timed path receives,
+    and the correlation matrix that step computed) as ``path``/<name>.npy, float32 or float64:
+
+    corr            n x n float64, K1's correlation matrix
+    removed_level   n x n float32, depth at which the pair was removed, -1 = the edge survives
+    sep_xy          R x 2 float32, ordered removed pairs with a non-empty separating-set union
+    sep_bits_u32    R x 2W float64, the unions' node bits as the 32-bit halves of each 64-bit word
+                    (low half first)
+    deg_levels      n x levels float32, node degrees at the start of each depth
+    tests_per_level levels float64, unique CI tests of each depth
+
+    The pairs are written in (x, y) order, whatever order the device exported them in. An array
+    over its share of the 64 MB is cut to a seeded sample of its rows, and ``<name>_rows.npy``
+    holds their indices. Returns {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+    written = {}
+
+    def put(name, a, idx):
+        if idx is not None:
+            a = a[idx]
+            np.save(os.path.join(path, name + "_rows.npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = list(a.shape)
+
+    def put_within(name, a, budget):
+        put(name, a, _dump_rows(a.shape[0], a.nbytes // max(a.shape[0], 1), budget))
+
+    if C is not None:
+        put_within("corr", C.cpu().numpy().astype(np.float64, copy=False), DUMP_BUDGET["corr"])
+    put_within("removed_level", out.removed_level.astype(np.float32), DUMP_BUDGET["removed_level"])
+    xy, bits = out.sep_xy, np.ascontiguousarray(out.sep_bits)
+    halves = bits.view(np.uint32).reshape(bits.shape[0], 2 * bits.shape[1])
+    order = np.lexsort((xy[:, 1], xy[:, 0]))
+    xy, halves = xy[order], halves[order]
+    idx = _dump_rows(xy.shape[0], 4 * xy.shape[1] + 8 * halves.shape[1] + 16, DUMP_BUDGET["sep"])   # + 2 index rows
+    put("sep_xy", xy.astype(np.float32), idx)
+    put("sep_bits_u32", halves.astype(np.float64), idx)
+    put_within("deg_levels", np.asarray(out.deg_levels, np.float32).T, DUMP_BUDGET["small"])
+    put_within("tests_per_level", np.asarray(out.stats["tests"], np.float64), DUMP_BUDGET["small"])
+    return written
 
 
 OB_PC_PAGERANK_S_PER_CASE = 3.39   # BASELINE.md: paper Table 6, PC-PageRank, Online Boutique, 8-CPU machine
@@ -402,7 +471,11 @@ def rq2_main(args):
 def main():
     args = parse()
     if args.workload == "rq2":
+        if args.dump_outputs:
+            sys.exit("--dump-outputs writes the skeleton workload's outputs; it has none for --workload rq2")
         return rq2_main(args)
+    if args.steps < 1:
+        sys.exit("--steps must be at least 1")
     import torch
     from rcaeval_amd import _lib, synth
     from rcaeval_amd.engine import get_engine
@@ -453,6 +526,7 @@ def main():
         native = bool(flag.item())
 
     k1_events = []
+    last_corr = [None]      # --dump-outputs: the correlation matrix of the latest single-GPU step
 
     def one_step():
         t0 = time.perf_counter()
@@ -469,7 +543,10 @@ def main():
             from rcaeval_amd.dist import sharded_corr
             C = sharded_corr(eng, Xd)
         else:   # single GPU: K1 + skeleton in one C call (pcg_pc_skeleton), no host round trip between
-            return eng.corr_skeleton(Xd, alpha=args.alpha, max_depth=args.max_depth, flags=flags)[0]
+            o, C = eng.corr_skeleton(Xd, alpha=args.alpha, max_depth=args.max_depth, flags=flags)
+            if args.dump_outputs:
+                last_corr[0] = C
+            return o
         torch.cuda.synchronize()
         phases.append(("corr", time.perf_counter() - t0))
         if dist_path:
@@ -524,7 +601,13 @@ def main():
     k_ms = st["kernel_ms"][dmax]
     kname = dominant_kernel(dmax, args.full_p, eng.get_tuning("SCREEN_MASK"))
     roof = roofline_of(kname, int(st["tests"][dmax]), dmax, k_ms)
-    if world == 1:      # K1 alone (for its roofline), outside the timed steps
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, out, last_corr[0])
+        progress("outputs written: " + ", ".join(f"{k} {v}" for k, v in dumped.items()))
+    last_corr[0] = None
+    if world == 1 and not args.full:
+        corr_med = 0.0
+    elif world == 1:    # K1 alone (for its roofline), outside the timed steps
         for _ in range(4):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -548,7 +631,7 @@ def main():
     # threshold decisions elsewhere — NOT every test's p (pcgpu.h PCG_FLAG_FULL_P). Twice: the
     # first call sizes the exact-path list
     full_p = None
-    if not args.full_p and not args.no_full_p and world == 1:
+    if args.full and not args.full_p and not args.no_full_p and world == 1:
         progress("full-p comparison run")
         C = eng.corr(Xd)
         fl = _lib.PCG_FLAG_FULL_P | _lib.PCG_FLAG_RECORD
@@ -589,7 +672,7 @@ def main():
             "roofline": roof,
             "sampled_records": full_p,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             progress("CPU baseline")
             cb = cpu_baseline(X, args.alpha, args.cpu_depth, st["tests"], out.removed_level)
             ref = cb.pop("_ref")

@@ -41,7 +41,7 @@ if [ "$PART" = 1 ]; then
     cp $OUT/pmc_summary.json $OUT/${TAG}_valu_class_pmc_abl1.json
   fi
 else
-  step bench 900 python bench.py --steps 20 --warmup 3
+  step bench 900 python bench.py --full --steps 20 --warmup 3
   line bench bench_line
   step rq2 600 python bench.py --workload rq2 --steps 1 --warmup 1
   line rq2 rq2_bench_line

@@ -19,8 +19,8 @@ for step in "$@"; do
     smoke) run smoke 400 python -c "import __graft_entry__ as g; g.smoke()" ;;
     test)  run pytest_gpu 1200 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout-method thread -p no:cacheprovider ;;
     testall) run pytest_gpu 1200 python -u -m pytest tests -m gpu -v --timeout 600 --timeout-method thread ;;
-    bench) run bench 900 python bench.py --steps 3 --warmup 1 ;;
-    benchfast) run bench 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline ;;
+    bench) run bench 900 python bench.py --full --steps 3 --warmup 1 ;;
+    benchfast) run bench 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline ;;
     prof) run prof 900 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline ;;
     dist2) PCG_DIST_TRACE=1 PCG_BENCH_DEVICE=0 PCG_DIST_BACKEND=gloo run dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 2 --warmup 1 ;;
     sim) run sim 600 python tools/shard_sim.py ;;

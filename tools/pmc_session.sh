@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=gpurun_out
 mkdir -p $OUT
-B="python bench.py --steps 1 --warmup 1 --no-cpu-baseline"
+B="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline"
 run() {
   local name=$1; shift
   echo "[$(date +%T)] start $name" >> $OUT/pmc_status.log

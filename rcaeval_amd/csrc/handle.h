@@ -70,9 +70,8 @@ struct pcg_handle {
     bool own_stream = false;
     std::string err;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t lev[2 * PCG_MAX_LEVELS] = {};   // depth-boundary events (skeleton_once), read after the last depth
-    bool lev_on = false;
-    int lev_n = 0;
+    hipEvent_t lev[2] = {};          // the small-graph skeleton's kernel bracket (skeleton_small)
+    bool lev_on = false;             // inside a level-loop run (level_run_begin .. finish / abort)
 
     // scratch
     DevBuf screenq;                 // fp32 sweep -> fp64 screen list (k_level_lds_f -> k_screen)
@@ -140,7 +139,7 @@ struct pcg_handle {
     bool wavek = false;              // small class runs k_level_wave this depth (deep levels)
     bool nblk = false;               // small class stages per-node compact blocks (k_node_blocks) this depth
     bool l1z_pre = false;            // depth 1's per-edge C values (k_edge_c) enqueued by pcg_level_begin
-    bool nimg = false;               // ... as fp32 LDS images of k_level_lds_f (k_node_blocks_t<true>)
+    bool nimg = false;               // ... as fp32 LDS images of k_level_lds_f (k_node_blocks_t)
     DevBuf cblk, lmk;                // k_node_blocks: per-node compact correlation blocks, local masks
     int64_t bo_off = 0;              // int64 offset of the compact-block offsets in cpre / cpre_pin
     int64_t lpt_off = 0;             // ... of k_level_lds_f's dispatch order (int32 nps, then nord)
@@ -148,11 +147,9 @@ struct pcg_handle {
     hipEvent_t rev[PCG_MAX_LEVELS][2] = {};   // per-depth CI-test kernel brackets
     int64_t near_seen = 0;           // near-alpha entries copied so far (the device list accumulates)
     int64_t near_total_dev = 0;      // the device's cumulative near-alpha count at the last level end
-    int64_t near_pending = 0;        // the device list's length (capped) at the last level end
     bool defer_near = false;         // skeleton_once: near-alpha records copied once after the last depth
-    PinBuf near_pin;                 // their host staging
     int run_max_depth = -1;          // skeleton_once's max_depth (-1: unbounded, or the level-step API)
-    // skeleton_once's depth boundaries (the summaries' wall-clock stamps; PCG_KBRACKET = 0)
+    // skeleton_once's depth boundaries (the summaries' wall-clock stamps)
     std::vector<unsigned long long> lev_stamp;
     bool stamps = false;
     int wall_khz = 0;

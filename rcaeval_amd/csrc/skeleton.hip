@@ -42,37 +42,29 @@
 #include "fisherz_dev.h"
 #include "handle.h"
 
-namespace {
-
-constexpr int MODE_DECIDE = 0;
+// ---------------------------------------------------------------------------------------
+// Compile-time tunables: every PCG_ one this file has (depth 1's L1Z_U, L1Z_BS and L1Z_MCAP sit with
+// k_level1_z). An A/B variant is built with tools/build_variant.sh NAME "-DPCG_X=.." and loaded
+// through PCG_LIB_PATH; the run-time knobs (pcg_set_tuning / the environment) are api.hip's kTune.
+// Depth masks have bit (1 << d) per depth.
+// decisions
 #ifndef PCG_COND_TAU
-#define PCG_COND_TAU 1e-4     // conditioning guard of the fast paths (see decide)
+#define PCG_COND_TAU 1e-4       // conditioning guard of the fast paths (see decide)
 #endif
-constexpr int MODE_FULLP = 1;
-constexpr int MODE_EXACT = 2;
-// candidates c per lane task in k_level_lds_t, per depth (measured, tools/variant_bench.sh):
-// depth 2 groups of 6 (round 2: 0.314 -> 0.282 ms vs 8, which had been -28 % vs 4); depth 3 groups of 6 (fp32 sweep: 0.715 -> 0.688 ms vs 4; the fp64 form measured 4 ~ 6, 8 +15 %);
+#ifndef PCG_F32_KE
+#define PCG_F32_KE 32.0         // fp32 screen: E = 2 KE u32 (1 + nu^2) >= KE u32 (1 + nu)^2, 1.75x DESIGN §4.1's 18 u32 (1 + nu)^2
+#endif
+#ifndef PCG_TG_F32
+#define PCG_TG_F32 0x18         // depths whose T-group sweep is fp32-screened (k_level_lds_f) by default
+#endif
+// T-group kernels (k_level_lds_t, k_level_lds_f): candidates c per lane task, per depth (measured,
+// tools/variant_bench.sh): depth 2 groups of 6 (0.314 -> 0.282 ms vs 8, which had been -28 % vs 4);
+// depth 3 groups of 6 (fp32 sweep: 0.715 -> 0.688 ms vs 4; the fp64 form measured 4 ~ 6, 8 +15 %);
 // depth 4 groups of 6 at 3 waves/SIMD (168 VGPRs): fp64 VALU from one wave issues at most every
 // ~8 cycles with a ~50-cycle dependent latency (tools/micro/valu_occ.hip), so a third wave of 6
 // chains beats two waves of 8 (4.03 vs 4.29 ms; groups of 4 at 3 waves 4.46 ms)
 #ifndef PCG_TG2
 #define PCG_TG2 6
-#endif
-#ifndef PCG_TG_WC
-#define PCG_TG_WC 0   // T-group sweep: project candidates with w_c = C_TT^-1 M[T][c] (see k_level_lds_t)
-#endif
-#ifndef PCG_TG_Y2
-#define PCG_TG_Y2 0   // T-group sweep: two y per iteration at the depths whose bit is set (1 << d)
-#endif
-#ifndef PCG_TG_SGPR
-#define PCG_TG_SGPR 0x18 // T-group sweep, depths whose bit (1 << d) is set: per-y bookkeeping as wave
-                         // lane masks (SALU) instead of per-lane bits
-#endif
-#ifndef PCG_TG_SGPR_WIDE
-#define PCG_TG_SGPR_WIDE PCG_TG_SGPR   // the same for the wide (128-bit mask) class
-#endif
-#ifndef PCG_TG_SPLIT
-#define PCG_TG_SPLIT 0   // lane-mask sweep: split the y range around a shared candidate window (spills: slower)
 #endif
 #ifndef PCG_TG3
 #define PCG_TG3 6
@@ -80,6 +72,92 @@ constexpr int MODE_EXACT = 2;
 #ifndef PCG_TG4
 #define PCG_TG4 6
 #endif
+// k_level_lds_t: blocks per CU each depth is register-sized for: 4 (128 VGPRs) at depths 2-3, 3
+// (168 VGPRs) for depth 4's groups of 6
+#ifndef PCG_MB2
+#define PCG_MB2 4
+#endif
+#ifndef PCG_MB3
+#define PCG_MB3 4
+#endif
+#ifndef PCG_MB4
+#define PCG_MB4 3
+#endif
+#ifndef PCG_TG_SGPR
+#define PCG_TG_SGPR 0x18        // k_level_lds_t depths whose per-y bookkeeping is wave lane masks (SALU), not per-lane bits
+#endif
+#ifndef PCG_TG_SGPR_WIDE
+#define PCG_TG_SGPR_WIDE PCG_TG_SGPR   // the same for the wide (128-bit mask) class
+#endif
+// k_level_lds_f
+#ifndef PCG_MBF2
+#define PCG_MBF2 4              // blocks per CU of the narrow class's launch bounds, per depth
+#endif
+#ifndef PCG_MBF3
+#define PCG_MBF3 4
+#endif
+#ifndef PCG_MBF4
+#define PCG_MBF4 4
+#endif
+#ifndef PCG_WIDE_MB
+#define PCG_WIDE_MB 2           // ... of the wide class
+#endif
+#ifndef PCG_TGF_SGPR
+#define PCG_TGF_SGPR 0x18       // depths whose per-y bookkeeping is in wave lane masks (depth 3 joined once the
+                                // memo skips were counted per node: 0.52 -> 0.49 ms)
+#endif
+#ifndef PCG_TGF_SR
+#define PCG_TGF_SR 4            // narrow class gathering A~ from C: rows per wave with loads in flight
+#endif
+#ifndef PCG_TGF_LPT
+#define PCG_TGF_LPT 0x10        // depths whose narrow class is dispatched largest degree first (LevelArgs::nord;
+                                // config 5 depth 4: kernel 1.715-1.74 -> 1.69-1.70 ms A/B; depth 3 measured
+                                // 0.68-0.69 -> 0.69-0.72: its largest-degree blocks staged together first)
+#endif
+#ifndef PCG_SCREEN_BUF
+#define PCG_SCREEN_BUF 96       // screen list entries a block buffers in LDS before its one counter atomic
+                                // (config 5 depth 3: kernel 0.68 ms with a global atomic per push, 0.44 without pushes)
+#endif
+#ifndef PCG_TGF_ABL
+#define PCG_TGF_ABL 0           // ablation builds for timing (tools/roofline_model.py --regions): 1 = tasks without
+                                // their sweeps, 2 = no tasks (staging and block overhead only); results are wrong
+#endif
+#ifndef PCG_TGF_ABL_D
+#define PCG_TGF_ABL_D 4         // the depth the ablation applies to (the narrow class only)
+#endif
+#ifndef PCG_TGF_PROF
+#define PCG_TGF_PROF 0          // diagnostic builds only: per-phase shader-clock cycles of k_level_lds_f at depth
+                                // PCG_TGF_PROF (narrow class) summed into g_tgf_prof, printed per level to stderr
+#endif
+#ifndef PCG_TGF_BLKT
+#define PCG_TGF_BLKT 0          // diagnostic builds only: per-block wall-clock (start, end, D, tasks) of k_level_lds_f at
+                                // depth PCG_TGF_BLKT (narrow class: g_blkt, wide: g_blkw), summarised per level on stderr
+#endif
+// k_level_lds
+#ifndef PCG_LDS_DEEP_TOP
+#define PCG_LDS_DEEP_TOP 20     // instantiations beyond PCG_MAX_DEPTH (threshold mode), 12..20; 17-20 spill to scratch
+#endif
+// level decomposition and launch order (level_begin_impl, pcg_level_run)
+#ifndef PCG_NB3_TARGET
+#define PCG_NB3_TARGET 4096     // narrow-class block target at depth 3 (best at 4096)
+#endif
+#ifndef PCG_NB4_TARGET
+#define PCG_NB4_TARGET 16384    // ... at depth 4, whose long per-node task lists otherwise leave a tail (2.53 -> 2.40 ms)
+#endif
+#ifndef PCG_L1_PAIRS
+#define PCG_L1_PAIRS 4096       // k_level1_pairs: neighbour pairs per chunk (1024 pairs 0.36 ms, 2048 0.243, 4096 0.192)
+#endif
+#ifndef PCG_REST_MAIN
+#define PCG_REST_MAIN 0x6       // depths whose wide / large class is the longer one: it runs on the main stream, the
+                                // narrow class on aux (the join then waits on an event that has usually fired)
+#endif
+// ---------------------------------------------------------------------------------------
+
+namespace {
+
+constexpr int MODE_DECIDE = 0;
+constexpr int MODE_FULLP = 1;
+constexpr int MODE_EXACT = 2;
 __host__ __device__ constexpr int tg_of_depth(int d) { return d == 2 ? PCG_TG2 : (d == 3 ? PCG_TG3 : PCG_TG4); }
 static_assert((PCG_TG2 == 4 || PCG_TG2 == 6 || PCG_TG2 == 8) && (PCG_TG3 == 4 || PCG_TG3 == 6 || PCG_TG3 == 8) &&
                   (PCG_TG4 == 4 || PCG_TG4 == 6 || PCG_TG4 == 8),
@@ -133,7 +211,7 @@ struct LevelArgs {
     int stamp_end;               // block 0 stamps ctr->t_run1 at entry (the kernel bracket's end)
 };
 
-// the kernel bracket's end (skeleton_once with PCG_KBRACKET = 0): one store by one thread
+// the kernel bracket's end (the level loop's device wall-clock stamps): one store by one thread
 __device__ __forceinline__ void stamp_run_end(const LevelArgs &a) {
     if (a.stamp_end && blockIdx.x == 0 && threadIdx.x == 0) a.ctr->t_run1 = wall_clock64();
 }
@@ -244,11 +322,7 @@ __device__ __forceinline__ void push_deferred(const LevelArgs &a, int x, int y, 
     }
 }
 
-#ifndef PCG_SCREEN_ABL
-#define PCG_SCREEN_ABL 0   // timing ablation only (wrong results): the fp32 sweep's screen pushes dropped
-#endif
 __device__ __forceinline__ void push_screen(const LevelArgs &a, int x, int y, const int *S, int d) {
-    if (PCG_SCREEN_ABL) return;
     const unsigned long long slot = atomicAdd(&a.ctr->screened, 1ull);
     if ((int64_t)slot < a.scr_cap) {
         ScreenEntry &e = a.screen[slot];
@@ -261,9 +335,6 @@ __device__ __forceinline__ void push_screen(const LevelArgs &a, int x, int y, co
 // global list with ONE counter atomic per block at its end: one returning atomic per entry on the
 // single list counter serialised at its L2 channel (config 5 depth 3: 8.9e4 pushes, kernel 0.68 ms;
 // 0.44 ms with the pushes dropped). A full buffer falls back to the per-entry push
-#ifndef PCG_SCREEN_BUF
-#define PCG_SCREEN_BUF 96
-#endif
 __device__ __forceinline__ void push_screen_blk(const LevelArgs &a, ScreenEntry *buf, unsigned *cnt, int x, int y,
                                                 const int *S, int d) {
     const unsigned k = atomicAdd(cnt, 1u);
@@ -985,9 +1056,6 @@ __global__ __launch_bounds__(256) void k_level(LevelArgs a) {
 // for (x, y | z): v = C_yz / sqrt(C_zz), c_xy = C_xy - u_z v, c_yy = C_yy - v^2.
 // A chunk is (x, a contiguous share of the D(D-1)/2 pairs, row-major over y < z).
 constexpr int L1_MAXD = 1024;
-#ifndef PCG_L1_ABL
-#define PCG_L1_ABL 0      // timing ablation only (wrong results): k_level1_pairs without its independence writes
-#endif
 constexpr int L1_PB = 4;              // pairs in flight per lane (independent gathers; 8 and 16 measured slower)
 size_t l1_lds_bytes(int D) { return (size_t)D * (4 + 5 * 8) + 16; }
 // I32: every index of C, adj and rm fits 31 bits (n * ldc < 2^31): 32-bit offsets instead of
@@ -1092,7 +1160,6 @@ __global__ __launch_bounds__(256) void k_level1_pairs(LevelArgs a) {
                     push_deferred(a, x, tg, sg, 1);
                 } else if (dec == 1) {
                     ++indep;
-                    if (PCG_L1_ABL) continue;      // timing ablation only (wrong results)
                     a.rm[(int64_t)x * a.n + tg] = 1;
                     a.rm[(int64_t)tg * a.n + x] = 1;
                     unsigned long long *row = reinterpret_cast<unsigned long long *>(
@@ -1111,7 +1178,7 @@ __global__ __launch_bounds__(256) void k_level1_pairs(LevelArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
-// depth 1 by conditioning node (threshold mode, one rank over the whole level; PCG_L1Z). The
+// depth 1 by conditioning node (threshold mode, one rank over the whole level; PCG_TUNE_L1Z). The
 // tests (x, t | z) with z in adj(x) are grouped by z: block z stages row z of C and of adj (both
 // contiguous) and walks x in adj(z), t in adj(x) \ {z}, so C_xt comes from the graph's per-edge
 // copy cxe[off[x] + j] = C[x][nbr[x][j]] (k_edge_c, read in CSR order) and C_tz, adj(t, z) from
@@ -1123,18 +1190,6 @@ __global__ __launch_bounds__(256) void k_level1_pairs(LevelArgs a) {
 // LDS (per-x terms staged once), so every lane has work and its loads of U items are in flight
 // together; the mirror union row of an independent pair is found from adj(t)'s bit rank (one
 // round of independent loads) instead of a binary search of nbr(t) (dependent loads).
-#ifndef PCG_L1Z
-#define PCG_L1Z 1
-#endif
-#ifndef PCG_L1Z_ABL
-#define PCG_L1Z_ABL 0     // timing ablation only (wrong results): 1 no mirror rows, 2 no independence writes
-#endif
-#ifndef PCG_L1Z_FLAT
-#define PCG_L1Z_FLAT 1    // 1: the sweep's common path without branches (depth-1 kernel 0.095 -> 0.090 ms); 0: k_level1_pairs' branch structure
-#endif
-#ifndef PCG_L1Z_DTE
-#define PCG_L1Z_DTE 1     // C_tt per edge in CSR order (k_edge_c) instead of a gather of diag[t] per item
-#endif
 #ifndef L1Z_U
 #define L1Z_U 4           // items in flight per lane
 #endif
@@ -1155,7 +1210,7 @@ __global__ __launch_bounds__(256) void k_edge_c(const double *C, int64_t ldc, co
     for (int j = lane; j < D; j += 64) {
         const int t = nbr[o + j];
         cxe[o + j] = Cx[t];
-        if (PCG_L1Z_DTE) dte[o + j] = diag[t];
+        dte[o + j] = diag[t];   // C_tt per edge in CSR order, instead of a gather of diag[t] per item
     }
 }
 
@@ -1244,56 +1299,36 @@ __global__ __launch_bounds__(L1Z_BS) void k_level1_z(LevelArgs a, const double *
                 es[q] = e;
                 ts[q] = t;
                 ce[q] = p < pw1 ? cxe[e] : 0.0;
-                if (PCG_L1Z_DTE) dt[q] = p < pw1 ? dte[e] : 0.0;
-            }
-            if (!PCG_L1Z_DTE) {
-#pragma unroll
-                for (int q = 0; q < L1Z_U; ++q) dt[q] = ts[q] != z ? a.diag[ts[q]] : 0.0;
+                dt[q] = p < pw1 ? dte[e] : 0.0;
             }
 #pragma unroll
             for (int q = 0; q < L1Z_U; ++q) {
                 const int t = ts[q];
                 const int xi = xs[q], x = sx[xi];
                 const bool adj_tz = (az[t >> 6] >> (t & 63)) & 1ull;
-                int dec = 2;
-                if (PCG_L1Z_FLAT) {
-                    // branch-free common path: every item is evaluated (t = z and the items past P
-                    // too, on defined values) and only a live test that is not certainly dependent
-                    // leaves it; decide<MODE_DECIDE>'s steps as selects (a NaN c_xx|z fails den > 0)
-                    const bool live = t != z && !(t < x && adj_tz);   // memo: (t, x | z) on t's side
-                    tests += live;
-                    const double cxx = scxx[xi];
-                    const double v = cz[t] * ri;
-                    const double cxt = ce[q] - su[xi] * v;
-                    const double ctt = dt[q] - v * v;
-                    const double den = cxx * ctt, num = cxt * cxt;
-                    const bool ok = den > 0.0 && den - num > kg;
-                    dec = !ok ? 2 : num < a.lo2 * den ? 1 : num > a.hi2 * den ? 0 : 2;
-                    if (!live || dec == 0) continue;
-                } else {
-                    if (t == z) continue;              // (also the items past P)
-                    if (t < x && adj_tz) continue;     // memo: node t's side holds (t, x | z)
-                    ++tests;
-                    const double cxx = scxx[xi];
-                    if (cxx == cxx) {
-                        double pv = 0.0;
-                        const double u = su[xi];
-                        const double v = cz[t] * ri;
-                        const double cxt = ce[q] - u * v;
-                        const double ctt = dt[q] - v * v;
-                        dec = decide<MODE_DECIDE>(a, cxt, cxx, ctt, kg, &pv);
-                    }
-                }
+                // branch-free common path (0.095 -> 0.090 ms against k_level1_pairs' branch structure):
+                // every item is evaluated (t = z and the items past P too, on defined values) and
+                // only a live test that is not certainly dependent leaves it; decide<MODE_DECIDE>'s
+                // steps as selects (a NaN c_xx|z fails den > 0)
+                const bool live = t != z && !(t < x && adj_tz);   // memo: (t, x | z) on t's side
+                tests += live;
+                const double cxx = scxx[xi];
+                const double v = cz[t] * ri;
+                const double cxt = ce[q] - su[xi] * v;
+                const double ctt = dt[q] - v * v;
+                const double den = cxx * ctt, num = cxt * cxt;
+                const bool ok = den > 0.0 && den - num > kg;
+                const int dec = !ok ? 2 : num < a.lo2 * den ? 1 : num > a.hi2 * den ? 0 : 2;
+                if (!live || dec == 0) continue;
                 if (dec == 2) {
                     push_deferred(a, x, t, sg, 1);
                 } else if (dec == 1) {
                     ++indep;
-                    if (PCG_L1Z_ABL == 2) continue;
                     a.rm[(int64_t)x * n + t] = 1;
                     a.rm[(int64_t)t * n + x] = 1;
                     unsigned long long *row = reinterpret_cast<unsigned long long *>(a.ug + (int64_t)es[q] * W);
                     atomicOr(&row[z >> 6], 1ull << (z & 63));
-                    if (PCG_L1Z_ABL != 1 && adj_tz && t > x) {   // S in adj(t): also t's side of the pair
+                    if (adj_tz && t > x) {   // S in adj(t): also t's side of the pair
                         // its row (x's position in nbr(t)) is searched at the block's end, one lane per
                         // entry, so the search's dependent loads do not stall the sweep (inline past
                         // L1Z_MCAP entries)
@@ -1402,13 +1437,10 @@ __device__ void deep_band_exact(const LevelArgs &a, double *slot, int D, int d, 
 // (every T-group task decodes them): C(c, 1) = c gives c = rr; C(c, 2) = c (c - 1) / 2 gives
 // c = floor((1 + sqrt(1 + 8 rr)) / 2), fixed up by one either way (rr < C(128, 2): the fp32 root is
 // within 1e-4 of the exact one). Deeper positions search the LDS table tab[c * stride + ii + 1].
-#ifndef PCG_COLEX_CF
-#define PCG_COLEX_CF 1   // A/B: 0 = the table search at every position
-#endif
 template <typename R, typename TAB>
 __device__ __forceinline__ int colex_elem(int ii, R rr, int hi, const TAB *tab, int stride) {
-    if (PCG_COLEX_CF && ii == 0) return (int)rr;
-    if (PCG_COLEX_CF && ii == 1) {
+    if (ii == 0) return (int)rr;
+    if (ii == 1) {
         int c = (int)((1.0f + __builtin_sqrtf(1.0f + 8.0f * (float)rr)) * 0.5f);
         if ((R)(c * (c - 1) / 2) > rr) --c;
         else if ((R)((c + 1) * c / 2) <= rr) ++c;
@@ -1439,28 +1471,6 @@ __device__ __forceinline__ double rsq_nr(double x) {
     return r0 * fma(-0.5 * x * r0, r0, 1.5);
 }
 
-#ifndef PCG_LDS_EXACT_DM
-#define PCG_LDS_EXACT_DM 1   // depths 5-12 (threshold / full-p): one k_level_lds instantiation per depth
-#endif
-#ifndef PCG_LDS_COLSOLVE
-#define PCG_LDS_COLSOLVE 1   // k_level_lds beyond PCG_MAX_DEPTH: column-order forward solve (n = 1000 unlimited
-                             // depth: depths 13-16 5 % faster; at depth 9 it cost 30 %, so only there)
-#endif
-#ifndef PCG_LDS_RSQ
-#define PCG_LDS_RSQ 0        // k_level_lds beyond PCG_MAX_DEPTH: pivot reciprocals by rsq_nr (fewer VALU, but
-                             // measured slower: n = 1000 900 vs 850 ms — the allocation of depths 19-20 spills more)
-#endif
-#ifndef PCG_LDS_COLCHOL
-#define PCG_LDS_COLCHOL 0    // ... and the right-looking Cholesky there (same products, same order per entry;
-                             // measured slower: n = 1000 900 vs 850 ms, its upfront block load spills at d >= 18)
-#endif
-#ifndef PCG_LDS_DEEP_TOP
-#define PCG_LDS_DEEP_TOP 20   // k_level_lds instantiations beyond PCG_MAX_DEPTH (threshold mode), <= 20
-#endif
-#ifndef PCG_LDS_SPILL_MIN
-#define PCG_LDS_SPILL_MIN 1e7 // depths 17..20 (instantiations that spill to scratch) take the per-lane kernel
-                              // only for levels of at least this many tests (else the wave kernels)
-#endif
 static_assert(PCG_LDS_DEEP_TOP >= 12 && PCG_LDS_DEEP_TOP <= 20, "PCG_LDS_DEEP_TOP");
 template <int DM, int MODE>
 __global__ __launch_bounds__(256) void k_level_lds(LevelArgs a) {
@@ -1472,7 +1482,7 @@ __global__ __launch_bounds__(256) void k_level_lds(LevelArgs a) {
     int lo = chunk_node(a.cpre, a.n, chunk);
     const int x = lo;
     const int D = a.deg[x];
-    const int d = (DM <= 4 || (MODE != MODE_EXACT && PCG_LDS_EXACT_DM)) ? DM : a.d;
+    const int d = (DM <= 4 || MODE != MODE_EXACT) ? DM : a.d;   // (the exact mode's instantiations are per depth bucket and read a.d)
     const int32_t *nxg = a.nbr + a.off[x];
 
     double *M = reinterpret_cast<double *>(smem);                 // D * D
@@ -1660,38 +1670,6 @@ __global__ __launch_bounds__(256) void k_level_lds(LevelArgs a) {
             bool ok = true;
             double gmin = 1.0;
             double uu = 0.0;
-            if constexpr (PCG_LDS_COLSOLVE && DM > PCG_MAX_DEPTH && PCG_LDS_COLCHOL) {
-                // right-looking (column) order, as the forward solve below: step j finishes column j
-                // and updates the trailing entries and u's partial sums — independent updates, and
-                // every entry subtracts the same products in the same (ascending) order as the
-                // left-looking form: identical results
-                double tu[DM];
-    #pragma unroll
-                for (int i = 0; i < DM; ++i) {
-                    tu[i] = Mx[k[i]];
-    #pragma unroll
-                    for (int m = 0; m <= i; ++m) L[i][m] = M[k[i] * D + k[m]];
-                }
-    #pragma unroll
-                for (int j = 0; j < DM; ++j) {
-                    const double sj = L[j][j];
-                    ok = ok && (sj > 0.0);
-                    gmin = fmin(gmin, sj);
-                    const double ljj = sqrt(sj);
-                    rinv[j] = 1.0 / ljj;
-                    L[j][j] = ljj;
-                    u[j] = tu[j] * rinv[j];
-                    uu += u[j] * u[j];
-    #pragma unroll
-                    for (int i = j + 1; i < DM; ++i) L[i][j] = L[i][j] * rinv[j];
-    #pragma unroll
-                    for (int i = j + 1; i < DM; ++i) {
-                        tu[i] -= L[i][j] * u[j];
-    #pragma unroll
-                        for (int m = j + 1; m <= i; ++m) L[i][m] -= L[i][j] * L[m][j];
-                    }
-                }
-            } else {
     #pragma unroll
             for (int j = 0; j < DM; ++j) {
                 if (j < d) {
@@ -1701,17 +1679,11 @@ __global__ __launch_bounds__(256) void k_level_lds(LevelArgs a) {
                         if (q < j) s -= L[j][q] * L[j][q];
                     ok = ok && (s > 0.0);
                     gmin = fmin(gmin, s);
-                    if constexpr (DM > PCG_MAX_DEPTH && PCG_LDS_RSQ) {
-                        // threshold mode only: 1 / sqrt by the fp32 estimate + one Newton step
-                        // (1e-14 relative, far inside the +-1e-6 band) instead of an IEEE sqrt and
-                        // divide; a pivot below 1e-30 is clamped, and its tiny gmin keeps every
-                        // test of the set off the decision (guard tau / gmin), so it goes exact
-                        rinv[j] = rsq_nr(fmax(s, 1e-30));
-                    } else {
-                        const double ljj = sqrt(s);
-                        rinv[j] = 1.0 / ljj;
-                        L[j][j] = ljj;
-                    }
+                    // (rsq_nr for the pivot reciprocals and a right-looking Cholesky both measured
+                    // slower beyond PCG_MAX_DEPTH: n = 1000 900 vs 850 ms, depths 18-20 spill more)
+                    const double ljj = sqrt(s);
+                    rinv[j] = 1.0 / ljj;
+                    L[j][j] = ljj;
     #pragma unroll
                     for (int i = 0; i < DM; ++i) {
                         if (i > j && i < d) {
@@ -1735,7 +1707,6 @@ __global__ __launch_bounds__(256) void k_level_lds(LevelArgs a) {
                     uu += u[i] * u[i];
                 }
             }
-            }
             const double cxx = Cxx - uu;
             ok = ok && (cxx == cxx);
 
@@ -1751,8 +1722,9 @@ __global__ __launch_bounds__(256) void k_level_lds(LevelArgs a) {
                 if (ok) {
                     const double *Mt = M + t * D;
                     double vv = 0.0, uv = 0.0;
-                    if constexpr (PCG_LDS_COLSOLVE && DM > PCG_MAX_DEPTH) {
-                        // the forward solve column by column: step q finishes v_q and updates every
+                    if constexpr (DM > PCG_MAX_DEPTH) {
+                        // the forward solve column by column (n = 1000 unlimited depth: depths 13-16
+                        // 5 % faster; at depth 9 it cost 30 %, so only beyond PCG_MAX_DEPTH): step q finishes v_q and updates every
                         // later row's partial sum, so the d - q - 1 updates of a step are
                         // independent (the row-by-row form gave the scheduler one dependent fp64
                         // chain at the one wave per SIMD of the deep instantiations). Each row's
@@ -1858,17 +1830,6 @@ __global__ __launch_bounds__(256) void k_level_lds(LevelArgs a) {
 //   v_c = (M[c][y] - l_c.v_T) / lambda_c,  c_yy = byy - v_c^2,  c_xy = bxy - u_c v_c
 // — the same partial correlation, ~9 fp64 ops per test instead of ~26. Tasks (g, T): group
 // g covers c in [g*TG, g*TG+TG), T ranges over (d-1)-subsets of [g*TG+1, D) in colex order.
-// blocks per CU each depth's T-group kernel is register-sized for: 4 (128 VGPRs) at depths 2-3,
-// 3 (168 VGPRs) for depth 4's groups of 6
-#ifndef PCG_MB2
-#define PCG_MB2 4
-#endif
-#ifndef PCG_MB3
-#define PCG_MB3 4
-#endif
-#ifndef PCG_MB4
-#define PCG_MB4 3
-#endif
 __host__ __device__ constexpr int tg_minblocks(int DM) { return DM == 2 ? PCG_MB2 : (DM == 3 ? PCG_MB3 : PCG_MB4); }
 // WIDE: nodes with 64 < D <= WIDE_DEG (128) — the same kernel with 128-bit local masks (the
 // few high-degree nodes of depths 2-3 that the staged generic kernel used to take)
@@ -1932,12 +1893,8 @@ __device__ __forceinline__ void tgroup_pairs(int D, int x, const int32_t *nxs, c
 // The (g, t0) pair of T-group task `task`: the last q < np with ppre[q] <= task (ppre ascends,
 // ppre[np] = the task count > task). A lane's tasks ascend (stride = block size), so the search
 // gallops forward from the previous task's pair (ppre[from] <= task): one or two probes per task
-// instead of a log2(np) binary search of dependent LDS reads. PCG_TG_GALLOP: the kernels (bit 0
-// the fp64 k_level_lds_t, bit 1 the fp32 k_level_lds_f) that gallop; measured at config 5: depth 4
-// 1.93 vs 1.98 ms, depth 2 (fp64) 0.22 vs 0.21 ms, so the fp32 sweep only
-#ifndef PCG_TG_GALLOP
-#define PCG_TG_GALLOP 2
-#endif
+// instead of a log2(np) binary search of dependent LDS reads. Only the fp32 k_level_lds_f gallops;
+// measured at config 5: depth 4 1.93 vs 1.98 ms, but depth 2 (the fp64 k_level_lds_t) 0.22 vs 0.21 ms
 template <bool GALLOP>
 __device__ __forceinline__ int tg_pair_search(const unsigned *ppre, int np, unsigned task, int from) {
     int lq = GALLOP ? from : 0, hq = np;
@@ -1957,9 +1914,6 @@ __device__ __forceinline__ int tg_pair_search(const unsigned *ppre, int np, unsi
     return lq;
 }
 
-#ifndef PCG_TGT_BATCH
-#define PCG_TGT_BATCH 1   // k_level_lds_t stages M and the local masks row-batched (0: per element, A/B)
-#endif
 template <int DM, bool WIDE>
 __global__ __launch_bounds__(256, WIDE ? 1 : tg_minblocks(DM)) void k_level_lds_t(LevelArgs a) {
     using Mask = LMask<WIDE>;
@@ -1995,60 +1949,41 @@ __global__ __launch_bounds__(256, WIDE ? 1 : tg_minblocks(DM)) void k_level_lds_
         btab[e] = (unsigned)pcg_binom(a.binom, c, i);             // <= C(64, 4): fits 32 bits
     }
     __syncthreads();
-    if (PCG_TGT_BATCH) {
-        // rows of M and of the local adjacency masks: a wave takes SR rows at a time, lane k column
-        // k (+ 64: WIDE), so SR x H x (C entry, adjacency word) loads are in flight per lane before
-        // the first is used (the per-element loop below waits out one gather round trip per ~8
-        // entries of a thread: ~20 dependent round trips per block at D = 45, ~64 at D = 128)
-        constexpr int H = WIDE ? 2 : 1, SR = WIDE ? 2 : 4;
-        const int lane = tid & 63, wv = tid >> 6, nwv = bs >> 6;
-        int kg[H];
+    // rows of M and of the local adjacency masks: a wave takes SR rows at a time, lane k column
+    // k (+ 64: WIDE), so SR x H x (C entry, adjacency word) loads are in flight per lane before
+    // the first is used (a per-element loop waits out one gather round trip per ~8 entries of a
+    // thread: ~20 dependent round trips per block at D = 45, ~64 at D = 128)
+    constexpr int H = WIDE ? 2 : 1, SR = WIDE ? 2 : 4;
+    const int lane = tid & 63, wv = tid >> 6, nwv = bs >> 6;
+    int kg[H];
 #pragma unroll
-        for (int hh = 0; hh < H; ++hh) kg[hh] = lane + 64 * hh < D ? nxs[lane + 64 * hh] : -1;
-        for (int t0 = wv * SR; t0 < D; t0 += nwv * SR) {
-            double v[SR][H];
-            uint64_t w[SR][H];
+    for (int hh = 0; hh < H; ++hh) kg[hh] = lane + 64 * hh < D ? nxs[lane + 64 * hh] : -1;
+    for (int t0 = wv * SR; t0 < D; t0 += nwv * SR) {
+        double v[SR][H];
+        uint64_t w[SR][H];
 #pragma unroll
-            for (int r = 0; r < SR; ++r) {
-                const int rg = nxs[min(t0 + r, D - 1)];
+        for (int r = 0; r < SR; ++r) {
+            const int rg = nxs[min(t0 + r, D - 1)];
 #pragma unroll
-                for (int hh = 0; hh < H; ++hh) {
-                    const int k = kg[hh] < 0 ? 0 : kg[hh];
-                    v[r][hh] = a.C[(int64_t)rg * a.ldc + k];
-                    w[r][hh] = a.adj[(int64_t)rg * a.W + (k >> 6)];
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < SR; ++r) {
-                const int t = t0 + r;
-                if (t >= D) break;                   // wave-uniform
-                Mask m = 0;
-#pragma unroll
-                for (int hh = 0; hh < H; ++hh) {
-                    const int k = lane + 64 * hh;
-                    if (k < DS) M[t * DS + k] = kg[hh] >= 0 ? v[r][hh] : 0.0;
-                    const bool bit = kg[hh] >= 0 && ((w[r][hh] >> (kg[hh] & 63)) & 1ull);
-                    m |= (Mask)__ballot(bit) << (64 * hh);
-                }
-                if (lane == 0) lmask[t] = m;
+            for (int hh = 0; hh < H; ++hh) {
+                const int k = kg[hh] < 0 ? 0 : kg[hh];
+                v[r][hh] = a.C[(int64_t)rg * a.ldc + k];
+                w[r][hh] = a.adj[(int64_t)rg * a.W + (k >> 6)];
             }
         }
-    } else {
-        for (int e = tid; e < D * DS; e += bs) {
-            const int t = e / DS, k = e - t * DS;
-            M[e] = k < D ? a.C[(int64_t)nxs[t] * a.ldc + nxs[k]] : 0.0;
-        }
-        // local adjacency masks: one wave per row t, lane k reads the bit adj(nxs[t], nxs[k]) and the
-        // wave's ballot is the row's 64-bit word (64 independent loads in flight per row)
-        for (int t = tid >> 6; t < D; t += bs >> 6) {
-            const uint64_t *ar = a.adj + (int64_t)nxs[t] * a.W;
+#pragma unroll
+        for (int r = 0; r < SR; ++r) {
+            const int t = t0 + r;
+            if (t >= D) break;                   // wave-uniform
             Mask m = 0;
-            for (int k0 = 0; k0 < D; k0 += 64) {
-                const int k = k0 + (tid & 63);
-                const bool bit = k < D && ((ar[nxs[k] >> 6] >> (nxs[k] & 63)) & 1ull);
-                m |= (Mask)__ballot(bit) << k0;
+#pragma unroll
+            for (int hh = 0; hh < H; ++hh) {
+                const int k = lane + 64 * hh;
+                if (k < DS) M[t * DS + k] = kg[hh] >= 0 ? v[r][hh] : 0.0;
+                const bool bit = kg[hh] >= 0 && ((w[r][hh] >> (kg[hh] & 63)) & 1ull);
+                m |= (Mask)__ballot(bit) << (64 * hh);
             }
-            if ((tid & 63) == 0) lmask[t] = m;
+            if (lane == 0) lmask[t] = m;
         }
     }
     for (int t = tid; t < D; t += bs) {
@@ -2088,7 +2023,7 @@ __global__ __launch_bounds__(256, WIDE ? 1 : tg_minblocks(DM)) void k_level_lds_
     int lq_prev = 0;
     for (uint64_t task = r0 + tid; task < r1; task += bs) {
         // (g, t0) pair of this task: the last pair whose prefix is <= task
-        int lq = tg_pair_search<(PCG_TG_GALLOP & 1) != 0>(ppre, np, (unsigned)task, lq_prev);
+        int lq = tg_pair_search<false>(ppre, np, (unsigned)task, lq_prev);
         lq_prev = lq;
         const int info = pinfo[lq];
         const int cbase = (info >> 8) * TG;
@@ -2192,23 +2127,6 @@ __global__ __launch_bounds__(256, WIDE ? 1 : tg_minblocks(DM)) void k_level_lds_
             okc[jj] = valid && okT && (lam2 > 0.0) && (cxx > 0.0);
             if (valid) gmin = fmin(gmin, lam2);
         }
-#if PCG_TG_WC
-        // w_c = L_T^-T l_c = C_TT^-1 M[T][c]: then l_c . v_T = w_c . M[T][y], so each candidate's
-        // chain starts from the row loads instead of waiting for v_T (same count of FMAs)
-#pragma unroll
-        for (int jj = 0; jj < TG; ++jj) {
-            double w[DT];
-#pragma unroll
-            for (int i = 0; i < DT; ++i) {
-                double t = 0.0;
-#pragma unroll
-                for (int k = i; k < DT; ++k) t += Li[k][i] * lc[jj][k];
-                w[i] = t;
-            }
-#pragma unroll
-            for (int i = 0; i < DT; ++i) lc[jj][i] = w[i];
-        }
-#endif
         // conditioning guard (see decide): c_xx c_yy - c_xy^2 > tau / g, with c_xx c_yy
         // recovered from the threshold product th = hi2 c_xx c_yy the sweep forms anyway
         const double inv_hi2 = 1.0 / a.hi2;
@@ -2267,9 +2185,9 @@ __global__ __launch_bounds__(256, WIDE ? 1 : tg_minblocks(DM)) void k_level_lds_
                     vv += v * v;
                     uv += uT[i] * v;
                 }
-                double projv[DT];
+                double projv[DT];   // l_c . v_T's second operand
 #pragma unroll
-                for (int i = 0; i < DT; ++i) projv[i] = PCG_TG_WC ? mT[i] : vT[i];
+                for (int i = 0; i < DT; ++i) projv[i] = vT[i];
                 const double byy = Md[t] - vv;
                 const double bxy = Mx[t] - uv;
 #pragma unroll
@@ -2277,9 +2195,10 @@ __global__ __launch_bounds__(256, WIDE ? 1 : tg_minblocks(DM)) void k_level_lds_
 #pragma unroll
                     for (int jj = 0; jj < NC; ++jj) sc[jj] -= lc[jj][i] * projv[i];
                 // lanes whose usable candidates are not all dependent at this y
-                // YM 0: no candidate equals y for any lane (a shared window outside y); 1: shared
-                // window holding y (candidate t - cb0 is y: masked by its scalar index); 2: lanes
-                // with different windows (a lane whose window holds y takes the rare path)
+                // YM 1: the wave's lanes share one candidate window (candidate t - cb0, if in it, is
+                // y: masked by its scalar index); 2: lanes with different windows (a lane whose
+                // window holds y takes the rare path). Splitting the y range around a shared window
+                // spilled and measured slower
                 const int jdead = YM == 1 ? t - cb0 : -1;
                 unsigned long long bad = 0ull;
 #pragma unroll
@@ -2354,24 +2273,16 @@ __global__ __launch_bounds__(256, WIDE ? 1 : tg_minblocks(DM)) void k_level_lds_
                     }
                 }
             };
-            using Y0 = std::integral_constant<int, 0>;
-            using Y1 = std::integral_constant<int, 1>;
-            using Y2 = std::integral_constant<int, 2>;
-            if (PCG_TG_SPLIT && uni) {
-                const int w0 = min(cb0, D), w1 = min(cb0 + TG, D);
-                for (int t = 0; t < w0; ++t) ystep(t, Y0{});
-                for (int t = w0; t < w1; ++t) ystep(t, Y1{});
-                for (int t = w1; t < D; ++t) ystep(t, Y0{});
-            } else if (uni) {
-                for (int t = 0; t < D; ++t) ystep(t, Y1{});
+            if (uni) {
+                for (int t = 0; t < D; ++t) ystep(t, std::integral_constant<int, 1>{});
             } else {
-                for (int t = 0; t < D; ++t) ystep(t, Y2{});
+                for (int t = 0; t < D; ++t) ystep(t, std::integral_constant<int, 2>{});
             }
             return;
             }
-            // YU consecutive y per iteration: their chains are independent, so the in-order issue of
-            // one wave has twice the fp64 work in flight (PCG_TG_Y2)
-            constexpr int YU = ((PCG_TG_Y2 >> DM) & 1) ? 2 : 1;
+            // one y per iteration: YU = 1 (kept in its unrolled-by-YU shape, from which the compiler's
+            // schedule of this loop comes; a direct one-y loop generates different code)
+            constexpr int YU = 1;
             for (int t0y = 0; t0y < D; t0y += YU) {
                 int tt[YU];
                 Mask lmv[YU];
@@ -2411,7 +2322,7 @@ __global__ __launch_bounds__(256, WIDE ? 1 : tg_minblocks(DM)) void k_level_lds_
                         uv += uT[i] * v;
                     }
 #pragma unroll
-                    for (int i = 0; i < DT; ++i) projv[k][i] = PCG_TG_WC ? mT[i] : vT[i];   // w_c.M[T][y] or l_c.v_T
+                    for (int i = 0; i < DT; ++i) projv[k][i] = vT[i];   // l_c . v_T's second operand
                     byy[k] = Md[t] - vv;
                     bxy[k] = Mx[t] - uv;
                     // live candidates: valid, c != y, and not deduplicated onto y (S in adj(y), y < x)
@@ -2554,9 +2465,6 @@ __global__ __launch_bounds__(256, WIDE ? 1 : tg_minblocks(DM)) void k_level_lds_
 // decides it like the fp64 kernels (band -> exact path). Decisions are therefore the fp64
 // kernels' decisions; only where the fp32 sweep is certain does it decide.
 typedef float f2v __attribute__((ext_vector_type(2)));
-#ifndef PCG_NODE_IMG
-#define PCG_NODE_IMG 1    // compact node blocks as fp32 LDS images of k_level_lds_f (DMA-staged), else fp64 rows
-#endif
 // k_level_lds_f's staged region of a node of degree D: M (D rows of DS floats, columns >= D zero),
 // the DS y records (2 mb bytes each) and nxs (DS ints). Narrow (mb = 8): rounded to 1 KB, the unit a
 // wave's LDS-DMA instruction writes (64 lanes x 16 B), so a node image is copied whole
@@ -2569,51 +2477,6 @@ struct alignas(16) YRecN {       // k_level_lds_f (narrow): a y's {A~_yy, A~_xy}
     unsigned long long lm;
 };
 constexpr double F32_U = 5.9604644775390625e-08;   // 2^-24
-#ifndef PCG_F32_KE
-#define PCG_F32_KE 32.0   // E = 2 KE u32 (1 + nu^2) >= KE u32 (1 + nu)^2, 1.75x DESIGN §4.1's 18 u32 (1 + nu)^2
-#endif
-#ifndef PCG_FORK_LATE
-#define PCG_FORK_LATE 1   // the aux stream's fork wait after the main stream's first class launch (0: before it)
-#endif
-#ifndef PCG_TG_F32
-#define PCG_TG_F32 0x18   // depths (bit 1 << d) whose T-group sweep is fp32-screened by default
-#endif
-#ifndef PCG_TGF_SGPR
-#define PCG_TGF_SGPR 0x18 // k_level_lds_f depths (bit 1 << d) whose per-y bookkeeping is in wave lane masks
-                          // (depth 3 joined in round 6 once the memo skips were counted per node: 0.52 -> 0.49 ms)
-#endif
-#ifndef PCG_KBRACKET
-#define PCG_KBRACKET 0       // skeleton_once's depth / kernel brackets: 1 timing events (each one a ~6 us marker
-                             // on the device's critical path), 0 device wall-clock stamps in kernels already queued
-#endif
-#ifndef PCG_LAST_XINL
-#define PCG_LAST_XINL 1      // the last depth of a max_depth-bounded run exports on the handle's stream
-#endif
-#ifndef PCG_NBLK_T
-#define PCG_NBLK_T 1         // compact node blocks built transposed (k_node_blocks_t) when C's row fits in LDS
-#endif
-#ifndef PCG_TGF_Y3FAST
-#define PCG_TGF_Y3FAST 1     // per-lane y loop (YM 3): skip the dependence-bit packing when no lane needs it
-#endif
-#ifndef PCG_TGF_PREFETCH
-#define PCG_TGF_PREFETCH 0  // k_level_lds_f depths (bit 1 << d) whose per-lane y loop prefetches row t + 1
-                             // (depth 3: 0.703 vs 0.698 ms without it; measured no gain, off)
-#endif
-#ifndef PCG_TGF_ABL
-#define PCG_TGF_ABL 0     // k_level_lds_f ablation builds for timing (tools/build_variant.sh): 1 = tasks without their
-                          // sweeps, 2 = no tasks (staging and block overhead only); results are wrong
-#endif
-#ifndef PCG_TGF_ABL_D
-#define PCG_TGF_ABL_D 4   // the depth the ablation applies to (the narrow class only)
-#endif
-#ifndef PCG_TGF_PROF
-#define PCG_TGF_PROF 0    // diagnostic builds only: per-phase shader-clock cycles of k_level_lds_f at depth
-                          // PCG_TGF_PROF (narrow class) summed into g_tgf_prof, printed per level to stderr
-#endif
-#ifndef PCG_TGF_BLKT
-#define PCG_TGF_BLKT 0    // diagnostic builds only: per-block wall-clock (start, end, D, tasks) of k_level_lds_f at
-                          // depth PCG_TGF_BLKT (narrow class: g_blkt, wide: g_blkw), summarised per level on stderr
-#endif
 #if PCG_TGF_BLKT
 constexpr int BLKT_MAX = 32768;
 __device__ unsigned long long g_blkt[BLKT_MAX][4];
@@ -2621,49 +2484,6 @@ __device__ unsigned long long g_blkw[4096][4];
 #endif
 #if PCG_TGF_PROF
 __device__ unsigned long long g_tgf_prof[8];   // block, staging, setup, sweep cycles (per wave); tasks; y iters; waves
-#endif
-#ifndef PCG_TGF_PKV
-#define PCG_TGF_PKV 1     // k_level_lds_f: v_T = L_T^-1 m_T with two of its rows as one packed chain (A/B: 0)
-#endif
-#ifndef PCG_TGF_SPLIT
-#define PCG_TGF_SPLIT 1   // k_level_lds_f, one candidate window per wave: y outside the window without the
-                          // dead-candidate selects (depth 4: 2.24 -> 2.09 ms once the rare-path values were opaque)
-#endif
-#ifndef PCG_TGF_SR
-#define PCG_TGF_SR 4      // k_level_lds_f, narrow class gathering A~ from C: rows per wave with loads in flight
-#endif
-#ifndef PCG_NB3_TARGET
-#define PCG_NB3_TARGET 4096   // narrow-class block target at depth 3 (level_begin_impl)
-#endif
-#ifndef PCG_NB4_TARGET
-#define PCG_NB4_TARGET 16384  // ... at depth 4
-#endif
-#ifndef PCG_SCREEN_EXACT
-#define PCG_SCREEN_EXACT 1   // the fp32 sweep's level end: screen + exact path in one launch (k_screen_exact)
-#endif
-#ifndef PCG_TGF_LPT
-#define PCG_TGF_LPT 0x10  // depths (bit 1 << d) whose k_level_lds_f narrow class is dispatched largest degree first
-                          // (LevelArgs::nord; config 5 depth 4: kernel 1.715-1.74 -> 1.69-1.70 ms A/B; depth 3
-                          // measured 0.68-0.69 -> 0.69-0.72: its largest-degree blocks staged together first)
-#endif
-#ifndef PCG_TGF_NSKIP
-#define PCG_TGF_NSKIP 1   // lane-mask sweep: the node's memo skips counted once in closed form, so a lane that
-                          // owns y no longer takes the rare path just to subtract its skips
-#endif
-#ifndef PCG_TGF_PRIO
-#define PCG_TGF_PRIO 0    // k_level_lds_f depths (bit 1 << d) whose staging runs at raised wave priority (s_setprio)
-#endif
-#ifndef PCG_MBF2
-#define PCG_MBF2 4
-#endif
-#ifndef PCG_WIDE_MB
-#define PCG_WIDE_MB 2     // k_level_lds_f, wide class: blocks per CU of the launch bounds
-#endif
-#ifndef PCG_MBF3
-#define PCG_MBF3 4
-#endif
-#ifndef PCG_MBF4
-#define PCG_MBF4 4
 #endif
 __host__ __device__ constexpr int tgf_minblocks(int DM) { return DM == 2 ? PCG_MBF2 : (DM == 3 ? PCG_MBF3 : PCG_MBF4); }
 
@@ -2774,8 +2594,6 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
     unsigned *ppre = btab + (D + 1) * (DM + 1);                   // task prefix per (g, t0) pair
     unsigned short *pinfo = reinterpret_cast<unsigned short *>(ppre + tg_pairs(D, DM) + 1);  // g << 8 | t0
 
-    constexpr bool PRIO = (PCG_TGF_PRIO >> DM) & 1;
-    if (PRIO) __builtin_amdgcn_s_setprio(3);
     const bool img = !WIDE && a.img;
     if (img) {
         // the node's image (M, the y records, nxs) by LDS-DMA, 1 KB per wave instruction, every
@@ -2900,7 +2718,6 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
     const int tx = *s_tx;
     const int np = *s_np;
     const Mask recm = REC ? s_recm : (Mask)0;   // (threshold-mode builds: no record code in the sweep)
-    if (PRIO) __builtin_amdgcn_s_setprio(0);
 #if PCG_TGF_PROF
     if (PROF) prof_stage = clock64() - prof_t0;
 #endif
@@ -2912,7 +2729,7 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
     const uint64_t r1 = (ABL & 2) ? r0 : min(ntask, r0 + (uint64_t)bs * spl);   // (ablation: no tasks)
     unsigned long long tests = 0, indep = 0;
     constexpr bool SGK = (PCG_TGF_SGPR >> DM) & 1;
-    if (SGK && PCG_TGF_NSKIP && chunk == a.cpre[x]) {
+    if (SGK && chunk == a.cpre[x]) {
         // the lane-mask sweep counts every (y, S) of its tasks; the node's first chunk takes back
         // the memo skips in closed form: (x, y, S) with y < x (t < tx) and S within adj(y) is y's
         // test (SkeletonDiscovery.py's cache hit), C(|adj(x) & adj(y)|, d) of them per such y
@@ -2946,7 +2763,7 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
         const unsigned long long prof_a = PROF ? clock64() : 0ull;
         if (PROF) { ++prof_tasks; prof_y += D; }
 #endif
-        int lq = tg_pair_search<(PCG_TG_GALLOP & 2) != 0>(ppre, np, (unsigned)task, lq_prev);
+        int lq = tg_pair_search<true>(ppre, np, (unsigned)task, lq_prev);
         lq_prev = lq;
         const int info = pinfo[lq];
         const int cbase = (info >> 8) * TG;
@@ -3203,13 +3020,14 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
         auto sweep = [&](auto nc_tag) {
             constexpr int NC = decltype(nc_tag)::value;
             constexpr int NQ = NC / 2;
-            // YM 1: one candidate window per wave (lane masks, y = candidate masked by index);
-            // 2: windows differ (lane masks, such lanes to the rare path); 3: per-lane live and
-            // dependence bits (the depths where dedup skips are common: a lane that owns y is
-            // not sent down the rare path just to count its skips)
-            // the LDS operands of one y (row t of A~): the candidates' entries, the T entries, the
-            // {A~_yy, A~_xy} pair and the local adjacency mask. Loaded apart from their use so the
-            // y loop can issue row t + 1's reads before row t's arithmetic (PCG_TGF_PREFETCH)
+            // YM 0 / 1: one candidate window per wave, y outside / inside it (lane masks, y =
+            // candidate masked by index); 2: windows differ (lane masks, such lanes to the rare
+            // path); 3: per-lane live and dependence bits (the depths where dedup skips are common:
+            // a lane that owns y is not sent down the rare path just to count its skips).
+            // The LDS operands of one y (row t of A~): the candidates' entries, the T entries, the
+            // {A~_yy, A~_xy} pair and the local adjacency mask, loaded apart from their use (a
+            // y loop that issued row t + 1's reads before row t's arithmetic measured no gain: depth 3
+            // 0.703 vs 0.698 ms)
             struct YPre {
                 f2v sc[NQ];
                 float mT[DT];
@@ -3249,7 +3067,7 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
                 // of partial sums <= 2 in magnitude instead of k <= 1 plus one: the b_yy / b_xy error
                 // terms grow by 2u, inside DESIGN §4.1's 14 u (1 + nu)^2 and 9 u (1 + nu)^2)
                 f2v acc = -pre.md;
-                if constexpr (PCG_TGF_PKV && DT == 3) {
+                if constexpr (DT == 3) {
                     // v_1 and v_2 as one packed chain (the same roundings in the same order as the
                     // scalar chains: L_i0 m_0, + L_i1 m_1, + L_i2 m_2)
                     const f2v l0 = {Lif[1][0], Lif[2][0]}, l1 = {Lif[1][1], Lif[2][1]};
@@ -3258,7 +3076,7 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
                     vT[0] = Lif[0][0] * mT[0];
                     vT[1] = p[0];
                     vT[2] = fmaf(Lif[2][2], mT[2], p[1]);
-                } else if constexpr (PCG_TGF_PKV && DT == 2) {
+                } else if constexpr (DT == 2) {
                     const f2v l0 = {Lif[0][0], Lif[1][0]}, m0 = {mT[0], mT[0]};
                     const f2v p = l0 * m0;
                     vT[0] = p[0];
@@ -3301,9 +3119,8 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
                         const f2v nm = __builtin_elementwise_fma(cxy, cxy, -k1p[q]);
                         wq[q] = __builtin_elementwise_fma(-mp[q], cyy, nm);
                         hq[q] = __builtin_elementwise_fma(hhp[q], cyy, -k2p[q]);
-                        if (PCG_TGF_Y3FAST)
-                            dall &= __builtin_amdgcn_ballot_w64(__builtin_fabsf(wq[q][0]) < hq[q][0]) &
-                                    __builtin_amdgcn_ballot_w64(__builtin_fabsf(wq[q][1]) < hq[q][1]);
+                        dall &= __builtin_amdgcn_ballot_w64(__builtin_fabsf(wq[q][0]) < hq[q][0]) &
+                                __builtin_amdgcn_ballot_w64(__builtin_fabsf(wq[q][1]) < hq[q][1]);
                     }
                     const bool inTset = (bool)((Tmask >> t) & 1u);
                     const bool own = (t < tx) && ((lm & Tmask) == Tmask);
@@ -3314,7 +3131,7 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
                     const bool recy = REC && (bool)((recm >> t) & 1u);     // wave-uniform
                     // a lane in dall with every valid candidate usable has rare = 0 (dp & okm covers
                     // every live bit): the wave skips the bit packing when no lane is outside that
-                    if (PCG_TGF_Y3FAST && !recy && !((~dall | notok) & __builtin_amdgcn_read_exec())) return;
+                    if (!recy && !((~dall | notok) & __builtin_amdgcn_read_exec())) return;
                     unsigned dp = 0;
 #pragma unroll
                     for (int q = 0; q < NQ; ++q)
@@ -3358,17 +3175,17 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
                 const bool recy = REC && (bool)((recm >> t) & 1u);     // wave-uniform
                 unsigned long long rarel = ((~dall & __builtin_amdgcn_read_exec()) | notok) & ~inT;
                 if (YM == 2) rarel |= __builtin_amdgcn_ballot_w64((unsigned)(t - cbase) < (unsigned)nval);
-                if (!PCG_TGF_NSKIP && t < tx) rarel |= __builtin_amdgcn_ballot_w64((lm & Tmask) == Tmask) & ~inT;
                 if (recy) rarel = __builtin_amdgcn_read_exec() & ~inT;
                 if (!rarel) return;
                 if (!(rarel & lanebit)) return;
-                // rare path (this lane): live set and dedup skips as in k_level_lds_t
+                // rare path (this lane): live set and dedup skips as in k_level_lds_t (the skips
+                // themselves are counted once per node in closed form, above, so a lane that owns y
+                // does not take this path just to subtract them)
                 const bool own = (t < tx) && ((lm & Tmask) == Tmask);
                 const unsigned tb = ((unsigned)(t - cbase) < (unsigned)TG) ? (1u << (t - cbase)) : 0u;
                 const unsigned skip = own ? (unsigned)(lm >> cbase) : 0u;
                 if ((Tmask >> t) & 1u) return;
                 const unsigned live = vmask & ~tb & ~skip;
-                if (!PCG_TGF_NSKIP) tcount -= __popc(vmask & ~tb & skip);
 #pragma unroll
                 for (int jj = 0; jj < TG; ++jj)
                     if ((live >> jj) & 1u) {
@@ -3382,27 +3199,15 @@ __global__ __launch_bounds__(256, WIDE ? PCG_WIDE_MB : tgf_minblocks(DM)) void k
             using Y2 = std::integral_constant<int, 2>;
             using Y3 = std::integral_constant<int, 3>;
             if (!SG) {
-                if constexpr ((PCG_TGF_PREFETCH >> DM) & 1) {
-                    // software-pipelined: row t + 1's LDS reads are in flight during row t's
-                    // arithmetic (the loop was LDS-latency bound: s_waitcnt right after the reads)
-                    YPre cur = yload(0);
-                    for (int t = 0; t < D; ++t) {
-                        const YPre nxt = yload(t + 1 < D ? t + 1 : t);
-                        ystep(t, Y3{}, cur);
-                        cur = nxt;
-                    }
-                } else {
-                    for (int t = 0; t < D; ++t) ystep(t, Y3{}, yload(t));
-                }
-            } else if (uni && PCG_TGF_SPLIT) {
+                for (int t = 0; t < D; ++t) ystep(t, Y3{}, yload(t));
+            } else if (uni) {
                 // the window [cb0, cb0 + NC) is the only place a candidate can be y: outside it the
-                // check needs no per-candidate "c == y" selects (YM 0)
+                // check needs no per-candidate "c == y" selects (YM 0; depth 4: 2.24 -> 2.09 ms once
+                // the rare-path values were opaque)
                 const int w0 = min(cb0, D), w1 = min(cb0 + NC, D);
                 for (int t = 0; t < w0; ++t) ystep(t, Y0{}, yload(t));
                 for (int t = w0; t < w1; ++t) ystep(t, Y1{}, yload(t));
                 for (int t = w1; t < D; ++t) ystep(t, Y0{}, yload(t));
-            } else if (uni) {
-                for (int t = 0; t < D; ++t) ystep(t, Y1{}, yload(t));
             } else {
                 for (int t = 0; t < D; ++t) ystep(t, Y2{}, yload(t));
             }
@@ -3539,13 +3344,11 @@ __global__ __launch_bounds__(256) void k_screen(LevelArgs a) {
     screen_lanes<DM>(a, blockIdx.x, gridDim.x, [&](int x, int y, const int *sg) { push_deferred(a, x, y, sg, DM); });
 }
 
-#ifndef PCG_NODE_BLOCKS
-#define PCG_NODE_BLOCKS 0x10  // depths (bit 1 << d) whose fp32-screened narrow sweep stages compact node blocks
-                              // (depth 4: kernel 2.13-2.16 -> 2.08 ms, FETCH 1.8 -> 0.18 GB; depth 3 measured no gain)
-#endif
 // the per-node compact blocks of the nodes with a chunk in [s_lo, s_hi): C[adj(x) + x, adj(x) + x]
 // (row-major, stride D + 1, x last; each C entry read once, in C's own orientation) and the
-// local adjacency masks (bit k of row t: nbr t and nbr k adjacent)
+// local adjacency masks (bit k of row t: nbr t and nbr k adjacent). Staged at the depths of
+// PCG_TUNE_NODE_BLOCKS (depth 4: kernel 2.13-2.16 -> 2.08 ms, FETCH 1.8 -> 0.18 GB; depth 3 measured
+// no gain); this gathering form serves the graphs whose C row does not fit k_node_blocks_t's LDS
 __global__ __launch_bounds__(256) void k_node_blocks(LevelArgs a, int64_t s_lo, int64_t s_hi) {
     const int x = blockIdx.x;
     if (a.cpre[x + 1] <= s_lo || a.cpre[x] >= s_hi || a.cpre[x + 1] == a.cpre[x]) return;
@@ -3571,17 +3374,15 @@ __global__ __launch_bounds__(256) void k_node_blocks(LevelArgs a, int64_t s_lo, 
     }
 }
 
-// the same compact blocks, built transposed: one block per SOURCE row y stages C[y, :] and y's
-// adjacency row in LDS (coalesced reads, C read once per depth), then writes row iy of the block
-// of every node x whose block holds y (x in adj(y), and x = y itself for the block's last row):
-// cb_x[iy][k] = C[y][ids_x[k]] from LDS, and (iy < D_x) x's local mask of y. A wave per target
-// node; its rows are contiguous writes. k_node_blocks gathers the same entries from C's
+// the compact blocks built transposed, when C's row fits in LDS: one block per SOURCE row y stages
+// C[y, :] and y's adjacency row in LDS (coalesced reads, C read once per depth), then writes row iy
+// of the block of every node x whose block holds y (x in adj(y), and x = y itself). A wave per
+// target node; its rows are contiguous writes. k_node_blocks gathers the same entries from C's
 // scattered columns — FETCH ~13x the block bytes at config 5's depth 4.
-// IMG: the blocks are k_level_lds_f's fp32 LDS images instead (tgf_image_bytes, at bo[x] doubles):
+// The blocks are k_level_lds_f's fp32 LDS images (tgf_image_bytes, at bo[x] doubles), DMA-staged there:
 // row iy of M = fp32(C[y][ids_x[k]]) (zero-padded to DS), y's record {fp32(C[y][y]), ., local mask},
 // and from x's own row (y = x) every record's fp32(C[x][ids_x[k]]) and the id list — the values the
 // kernel's own staging computes, so the sweep's results are unchanged
-template <bool IMG>
 __global__ __launch_bounds__(256) void k_node_blocks_t(LevelArgs a, int64_t s_lo, int64_t s_hi, int maxdeg) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *row = reinterpret_cast<double *>(smem);
@@ -3620,7 +3421,7 @@ __global__ __launch_bounds__(256) void k_node_blocks_t(LevelArgs a, int64_t s_lo
     for (int t = wv; t <= Dy; t += nwv) {
         const int gn = t + nwv <= Dy ? load(t + nwv) : 0;
         const int x = tx[t];
-        if (IMG && x >= 0) {
+        if (x >= 0) {
             const int D = tD[t], DS = (D + 3) & ~3;
             float *img = reinterpret_cast<float *>(a.cblk + tbo[t]);
             float *Yr = img + D * DS;
@@ -3638,17 +3439,6 @@ __global__ __launch_bounds__(256) void k_node_blocks_t(LevelArgs a, int64_t s_lo
                     Yr[4 * iy] = (float)row[y];
                     *reinterpret_cast<unsigned long long *>(Yr + 4 * iy + 2) = m;
                 }
-            }
-        } else if (x >= 0) {
-            const int D = tD[t], L = D + 1;
-            const int iy = x == y ? D : __popcll(__ballot(lane < D && g < y));
-            double *cb = a.cblk + tbo[t] + (int64_t)iy * L;
-            if (lane < L) cb[lane] = row[g];                 // lane D: column x (g = x there)
-            if (L > 64 && lane == 0) cb[64] = row[x];        // D = 64: the block's last column
-            if (iy < D) {
-                const bool bit = lane < D && ((arow[g >> 6] >> (g & 63)) & 1ull);
-                const unsigned long long m = __ballot(bit);
-                if (lane == 0) a.lmk[toff[t] + iy] = m;
             }
         }
         g = gn;
@@ -4922,55 +4712,55 @@ LevelArgs make_args(pcg_handle *h, int d, int mode_exact_all) {
 }
 
 template <int MODE>
-void launch_level_mode(pcg_handle *h, const LevelArgs &a, int64_t nchunks, size_t lds) {
+void launch_level_mode(hipStream_t s, const LevelArgs &a, int64_t nchunks, size_t lds) {
     const dim3 grid((unsigned)nchunks), block((unsigned)a.bs);
     const int d = a.d;
-    if (d == 1) hipLaunchKernelGGL((k_level<1, MODE>), grid, block, lds, h->stream, a);
-    else if (d == 2) hipLaunchKernelGGL((k_level<2, MODE>), grid, block, lds, h->stream, a);
-    else if (d == 3) hipLaunchKernelGGL((k_level<3, MODE>), grid, block, lds, h->stream, a);
-    else if (d == 4) hipLaunchKernelGGL((k_level<4, MODE>), grid, block, lds, h->stream, a);
-    else if (d <= 6) hipLaunchKernelGGL((k_level<6, MODE>), grid, block, lds, h->stream, a);
-    else if (d <= 8) hipLaunchKernelGGL((k_level<8, MODE>), grid, block, lds, h->stream, a);
-    else hipLaunchKernelGGL((k_level<12, MODE>), grid, block, lds, h->stream, a);
+    if (d == 1) hipLaunchKernelGGL((k_level<1, MODE>), grid, block, lds, s, a);
+    else if (d == 2) hipLaunchKernelGGL((k_level<2, MODE>), grid, block, lds, s, a);
+    else if (d == 3) hipLaunchKernelGGL((k_level<3, MODE>), grid, block, lds, s, a);
+    else if (d == 4) hipLaunchKernelGGL((k_level<4, MODE>), grid, block, lds, s, a);
+    else if (d <= 6) hipLaunchKernelGGL((k_level<6, MODE>), grid, block, lds, s, a);
+    else if (d <= 8) hipLaunchKernelGGL((k_level<8, MODE>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((k_level<12, MODE>), grid, block, lds, s, a);
 }
 
 template <int MODE>
-void launch_lds_mode(pcg_handle *h, const LevelArgs &a, int64_t nchunks, size_t lds) {
+void launch_lds_mode(hipStream_t s, const LevelArgs &a, int64_t nchunks, size_t lds) {
     const dim3 grid((unsigned)nchunks), block(256);
     const int d = a.d;
-    if (d == 1) hipLaunchKernelGGL((k_level_lds<1, MODE>), grid, block, lds, h->stream, a);
-    else if (d == 2) hipLaunchKernelGGL((k_level_lds<2, MODE>), grid, block, lds, h->stream, a);
-    else if (d == 3) hipLaunchKernelGGL((k_level_lds<3, MODE>), grid, block, lds, h->stream, a);
-    else if (d == 4) hipLaunchKernelGGL((k_level_lds<4, MODE>), grid, block, lds, h->stream, a);
-    else if constexpr (MODE != MODE_EXACT && PCG_LDS_EXACT_DM) {
+    if (d == 1) hipLaunchKernelGGL((k_level_lds<1, MODE>), grid, block, lds, s, a);
+    else if (d == 2) hipLaunchKernelGGL((k_level_lds<2, MODE>), grid, block, lds, s, a);
+    else if (d == 3) hipLaunchKernelGGL((k_level_lds<3, MODE>), grid, block, lds, s, a);
+    else if (d == 4) hipLaunchKernelGGL((k_level_lds<4, MODE>), grid, block, lds, s, a);
+    else if constexpr (MODE != MODE_EXACT) {
         // one instantiation per depth: the per-lane Cholesky arrays sized by d, not by the bucket's
         // largest depth (k_level_lds<12> took 256 VGPRs + 1 AGPR, one wave per SIMD, at d = 9)
-        if (d == 5) hipLaunchKernelGGL((k_level_lds<5, MODE>), grid, block, lds, h->stream, a);
-        else if (d == 6) hipLaunchKernelGGL((k_level_lds<6, MODE>), grid, block, lds, h->stream, a);
-        else if (d == 7) hipLaunchKernelGGL((k_level_lds<7, MODE>), grid, block, lds, h->stream, a);
-        else if (d == 8) hipLaunchKernelGGL((k_level_lds<8, MODE>), grid, block, lds, h->stream, a);
-        else if (d == 9) hipLaunchKernelGGL((k_level_lds<9, MODE>), grid, block, lds, h->stream, a);
-        else if (d == 10) hipLaunchKernelGGL((k_level_lds<10, MODE>), grid, block, lds, h->stream, a);
-        else if (d == 11) hipLaunchKernelGGL((k_level_lds<11, MODE>), grid, block, lds, h->stream, a);
+        if (d == 5) hipLaunchKernelGGL((k_level_lds<5, MODE>), grid, block, lds, s, a);
+        else if (d == 6) hipLaunchKernelGGL((k_level_lds<6, MODE>), grid, block, lds, s, a);
+        else if (d == 7) hipLaunchKernelGGL((k_level_lds<7, MODE>), grid, block, lds, s, a);
+        else if (d == 8) hipLaunchKernelGGL((k_level_lds<8, MODE>), grid, block, lds, s, a);
+        else if (d == 9) hipLaunchKernelGGL((k_level_lds<9, MODE>), grid, block, lds, s, a);
+        else if (d == 10) hipLaunchKernelGGL((k_level_lds<10, MODE>), grid, block, lds, s, a);
+        else if (d == 11) hipLaunchKernelGGL((k_level_lds<11, MODE>), grid, block, lds, s, a);
         else if constexpr (MODE == MODE_DECIDE) {
             // beyond PCG_MAX_DEPTH (up to PCG_LDS_DEEP_TOP; use_wave sends deeper levels to the
             // one-wave-per-set kernels)
-            if (d == 13) hipLaunchKernelGGL((k_level_lds<13, MODE>), grid, block, lds, h->stream, a);
-            else if (d == 14) hipLaunchKernelGGL((k_level_lds<14, MODE>), grid, block, lds, h->stream, a);
-            else if (d == 15) hipLaunchKernelGGL((k_level_lds<15, MODE>), grid, block, lds, h->stream, a);
-            else if (d == 16) hipLaunchKernelGGL((k_level_lds<16, MODE>), grid, block, lds, h->stream, a);
+            if (d == 13) hipLaunchKernelGGL((k_level_lds<13, MODE>), grid, block, lds, s, a);
+            else if (d == 14) hipLaunchKernelGGL((k_level_lds<14, MODE>), grid, block, lds, s, a);
+            else if (d == 15) hipLaunchKernelGGL((k_level_lds<15, MODE>), grid, block, lds, s, a);
+            else if (d == 16) hipLaunchKernelGGL((k_level_lds<16, MODE>), grid, block, lds, s, a);
 #if PCG_LDS_DEEP_TOP > 16
-            else if (d == 17) hipLaunchKernelGGL((k_level_lds<17, MODE>), grid, block, lds, h->stream, a);
-            else if (d == 18) hipLaunchKernelGGL((k_level_lds<18, MODE>), grid, block, lds, h->stream, a);
-            else if (d == 19) hipLaunchKernelGGL((k_level_lds<19, MODE>), grid, block, lds, h->stream, a);
-            else if (d == 20) hipLaunchKernelGGL((k_level_lds<20, MODE>), grid, block, lds, h->stream, a);
+            else if (d == 17) hipLaunchKernelGGL((k_level_lds<17, MODE>), grid, block, lds, s, a);
+            else if (d == 18) hipLaunchKernelGGL((k_level_lds<18, MODE>), grid, block, lds, s, a);
+            else if (d == 19) hipLaunchKernelGGL((k_level_lds<19, MODE>), grid, block, lds, s, a);
+            else if (d == 20) hipLaunchKernelGGL((k_level_lds<20, MODE>), grid, block, lds, s, a);
 #endif
-            else hipLaunchKernelGGL((k_level_lds<12, MODE>), grid, block, lds, h->stream, a);
-        } else hipLaunchKernelGGL((k_level_lds<12, MODE>), grid, block, lds, h->stream, a);
+            else hipLaunchKernelGGL((k_level_lds<12, MODE>), grid, block, lds, s, a);
+        } else hipLaunchKernelGGL((k_level_lds<12, MODE>), grid, block, lds, s, a);
     } else {
-        if (d <= 6) hipLaunchKernelGGL((k_level_lds<6, MODE>), grid, block, lds, h->stream, a);
-        else if (d <= 8) hipLaunchKernelGGL((k_level_lds<8, MODE>), grid, block, lds, h->stream, a);
-        else hipLaunchKernelGGL((k_level_lds<12, MODE>), grid, block, lds, h->stream, a);
+        if (d <= 6) hipLaunchKernelGGL((k_level_lds<6, MODE>), grid, block, lds, s, a);
+        else if (d <= 8) hipLaunchKernelGGL((k_level_lds<8, MODE>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((k_level_lds<12, MODE>), grid, block, lds, s, a);
     }
 }
 
@@ -5039,24 +4829,6 @@ bool use_wave(const pcg_handle *h, int mode, int d, double tests) {
 // D(D-1)/2 neighbour pairs evenly, ~L1_PAIRS_PER_CHUNK each, so a high-degree node is spread
 // over many blocks instead of a D/256-chunk tail (measured: 1024 pairs 0.36 ms, 2048 0.243,
 // 4096 0.192)
-#ifndef PCG_L1_PAIRS
-#define PCG_L1_PAIRS 4096
-#endif
-#ifndef PCG_TAIL_SPIN
-#define PCG_TAIL_SPIN 1      // skeleton_once's last transfer: one kernel into host-coherent memory, host spin (0: blits + sync)
-#endif
-#ifndef PCG_TAIL_EARLY
-#define PCG_TAIL_EARLY 1     // the tail kernel queued behind the depth bound's last barrier (0: after the host read it)
-#endif
-#ifndef PCG_MAIN_FIRST
-#define PCG_MAIN_FIRST 1     // with PCG_REST_MAIN: the main-stream (longer) class launched before the forked one
-#endif
-#ifndef PCG_REST_MAIN
-#define PCG_REST_MAIN 0x6    // depths (bit 1 << d) whose wide / large class runs on the main stream, the narrow one on aux
-#endif
-#ifndef PCG_CLASS_ORDER
-#define PCG_CLASS_ORDER 0
-#endif
 constexpr int64_t L1_PAIRS_PER_CHUNK = PCG_L1_PAIRS;
 int mode_of(const pcg_handle *h, int d);
 bool use_l1_pairs(const pcg_handle *h, int d) { return d == 1 && mode_of(h, d) == MODE_DECIDE && h->maxdeg <= L1_MAXD; }
@@ -5142,11 +4914,6 @@ int graph_launch(pcg_handle *h) {
                        reinterpret_cast<int32_t *>(ds + 1), seq, nfill);
     h->cb = t;
     PCG_HIP(h, hipGetLastError());
-    if (h->lev_on && !h->stamps && h->lev_n < 2 * PCG_MAX_LEVELS) {   // depth boundary (skeleton_once), off the host's critical path
-        hipEvent_t &e = h->lev[h->lev_n++];
-        if (!e) PCG_HIP(h, hipEventCreate(&e));
-        PCG_HIP(h, hipEventRecord(e, h->stream));
-    }
     return PCG_OK;
 }
 
@@ -5308,12 +5075,9 @@ void level_start_stats(pcg_handle *h, int depth) {
 
 int level_begin_buffers(pcg_handle *h, int depth);
 
-#ifndef PCG_L1Z_EARLY
-#define PCG_L1Z_EARLY 1   // k_edge_c enqueued before the level's host decomposition (1) or behind the prefix copy
-#endif                    // (0: depth-1 level 0.165-0.174 vs 0.157-0.163 ms, two A/B passes on one box)
 // depth 1 by conditioning node (k_level1_z) over the whole level on one rank
 bool l1z_use(const pcg_handle *h, int d) {
-    return d == 1 && PCG_L1Z && h->tune[PCG_TUNE_L1Z] && mode_of(h, d) == MODE_DECIDE && !(h->flags & PCG_FLAG_RECORD) && h->world == 1 &&
+    return d == 1 && h->tune[PCG_TUNE_L1Z] && mode_of(h, d) == MODE_DECIDE && !(h->flags & PCG_FLAG_RECORD) && h->world == 1 &&
            l1z_lds_bytes(h->n, h->W, h->maxdeg) + 8 * L1Z_MCAP + 512 <= LDS_MAX;
 }
 
@@ -5343,7 +5107,9 @@ int level_begin_impl(pcg_handle *h, int depth, int64_t *total_chunks) {
     h->depth = depth;
     const int n = (int)h->n;
     h->l1z_pre = false;
-    if (PCG_L1Z_EARLY && l1z_use(h, depth)) {   // depth 1's per-edge C values run while the host decomposes
+    // depth 1's per-edge C values run while the host decomposes (enqueued behind the prefix copy
+    // instead: depth-1 level 0.165-0.174 vs 0.157-0.163 ms, two A/B passes on one box)
+    if (l1z_use(h, depth)) {
         if (int rc = l1z_edges(h)) return rc;
         h->l1z_pre = true;
     }
@@ -5402,7 +5168,7 @@ int level_begin_impl(pcg_handle *h, int depth, int64_t *total_chunks) {
         // compact node blocks (k_node_blocks) for the narrow class of the fp32-screened sweeps
         h->nblk = tg && use_screen32(h, depth) && ((h->tune[PCG_TUNE_NODE_BLOCKS] >> depth) & 1);
         // ... as fp32 LDS images when the transposed builder's row of C fits its LDS
-        h->nimg = h->nblk && PCG_NODE_IMG && PCG_NBLK_T &&
+        h->nimg = h->nblk &&
                   8 * (size_t)n + 8 * (size_t)h->W + (size_t)(maxd + 1) * (sizeof(int64_t) + 3 * sizeof(int)) <= 64 * 1024;
         std::vector<uint64_t> ns_of(maxd + 1, 0), units_of(maxd + 1, 0);
         std::vector<int> cls_of(maxd + 1, 2);
@@ -5529,11 +5295,6 @@ int level_begin_impl(pcg_handle *h, int depth, int64_t *total_chunks) {
         PCG_HIP(h, hipGetLastError());
     }
     PCG_HT(h, "begin:prefix-copy-launched");
-    // (PCG_L1Z_EARLY 0) depth 1's per-edge C values right behind the prefix copy
-    if (!h->l1z_pre && l1z_use(h, depth)) {
-        if (int rc = l1z_edges(h)) return rc;
-        h->l1z_pre = true;
-    }
     return level_begin_buffers(h, depth);
 }
 
@@ -5683,267 +5444,275 @@ extern "C" int pcg_level_split(pcg_handle *h, int rank, int world, int64_t *chun
     return PCG_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// pcg_level_run's pieces. Each launches on the stream it is given: a depth's node classes can run
+// side by side on two streams (run_classes).
+namespace {
+
+// a run-time v in [LO, HI] as a compile-time constant: f(std::integral_constant<int, v>{})
+template <int LO, int HI, typename F>
+void with_int(int v, F &&f) {
+    if constexpr (LO < HI) {
+        if (v <= LO) f(std::integral_constant<int, LO>{});
+        else with_int<LO + 1, HI>(v, f);
+    } else {
+        f(std::integral_constant<int, HI>{});
+    }
+}
+
+// the T-group sweeps of depth d = 2..4: fp32-screened (rec: the build with the record routing) or fp64
+template <bool WIDE>
+void launch_lds_f(int d, bool rec, int64_t nblocks, size_t lds, hipStream_t s, const LevelArgs &a) {
+    with_int<2, 4>(d, [&](auto dm) {
+        constexpr int DM = decltype(dm)::value;
+        if (rec) hipLaunchKernelGGL((k_level_lds_f<DM, WIDE, true>), dim3((unsigned)nblocks), dim3(256), lds, s, a);
+        else hipLaunchKernelGGL((k_level_lds_f<DM, WIDE>), dim3((unsigned)nblocks), dim3(256), lds, s, a);
+    });
+}
+template <bool WIDE>
+void launch_lds_t(int d, int64_t nblocks, size_t lds, hipStream_t s, const LevelArgs &a) {
+    with_int<2, 4>(d, [&](auto dm) {
+        hipLaunchKernelGGL((k_level_lds_t<decltype(dm)::value, WIDE>), dim3((unsigned)nblocks), dim3(256), lds, s, a);
+    });
+}
+
+// depth 0: the tiles of the pair triangle, then the forbidden pairs
+void run_depth0(pcg_handle *h, const LevelArgs &a, int mode, int64_t nch, hipStream_t s) {
+    const dim3 grid((unsigned)nch), block(256);
+    if (mode == MODE_DECIDE) hipLaunchKernelGGL(k_level0<MODE_DECIDE>, grid, block, 0, s, a);
+    else if (mode == MODE_FULLP) hipLaunchKernelGGL(k_level0<MODE_FULLP>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(k_level0<MODE_EXACT>, grid, block, 0, s, a);
+    if (h->banned && a.chunk_lo == 0) {
+        // background knowledge (pcg_set_forbidden_pairs): pairs forbidden in both
+        // directions leave at the end of depth 0 whatever their tests said
+        // (SkeletonDiscovery.py:86-101, stable branch). Rank 0's slice carries them
+        // into the merged flags in a sharded run.
+        const int64_t nn = (int64_t)h->n * h->n;
+        hipLaunchKernelGGL(k_or_flags, dim3((unsigned)std::min<int64_t>((nn + 255) / 256, 4096)), dim3(256), 0, s,
+                           h->banned, (int64_t)h->n, a.rm);
+    }
+}
+
+// the whole of depth 1 by conditioning node (k_level1_z)
+int run_depth1_z(pcg_handle *h, const LevelArgs &a, hipStream_t s) {
+    if (!h->l1z_pre)
+        if (int rc = l1z_edges(h)) return rc;
+    const int64_t S1 = std::max<int64_t>(h->sumdeg, 1);
+    const double *cxe = (const double *)h->cblk.p, *dte = cxe + S1;
+    hipLaunchKernelGGL(k_level1_z, dim3((unsigned)h->n), dim3(L1Z_BS), l1z_lds_bytes(h->n, h->W, h->maxdeg), s, a, cxe, dte);
+    return PCG_OK;
+}
+
+// the narrow class (LDS-resident kernels), chunks [s_lo, s_hi) of it
+void run_narrow(pcg_handle *h, const LevelArgs &a, int mode, int64_t s_lo, int64_t s_hi, hipStream_t s) {
+    if (s_hi <= s_lo) return;
+    const int d = a.d;
+    const int64_t nb = s_hi - s_lo;
+    LevelArgs as = a;
+    as.chunk_lo = s_lo;
+    as.bs = 256;
+    const int dl = h->tgroup ? (h->maxdeg_small + 3) & ~3 : h->maxdeg_small;
+    as.lds_btab_off = (int)lds_small_core(dl);
+    size_t lds = h->tgroup ? lds_tgroup_bytes(dl, d) : lds_small_bytes(dl);
+    if (!h->tgroup && d > PCG_MAX_DEPTH)   // k_level_lds's per-wave exact-path slots
+        lds = std::max(lds, lds_small_core(dl) + 4 * sizeof(double) * WAVE_SLOT_DOUBLES(PCG_LDS_DEEP_TOP));
+    if (h->wavek) {
+        const dim3 grid((unsigned)nb), block(256);
+        const size_t core = lds_small_core(h->maxdeg_small);
+        as.lds_btab_off = (int)core;
+        if (d <= 16) {
+            const size_t ldsw = core + 4 * sizeof(double) * (WAVE_SLOT_DOUBLES(16) + 16);
+            if (mode == MODE_DECIDE) hipLaunchKernelGGL((k_level_wave<16, MODE_DECIDE>), grid, block, ldsw, s, as);
+            else hipLaunchKernelGGL((k_level_wave<16, MODE_FULLP>), grid, block, ldsw, s, as);
+        } else {
+            const size_t ldsw = core + 4 * sizeof(double) * (WAVE_SLOT_DOUBLES(32) + 32);
+            if (mode == MODE_DECIDE) hipLaunchKernelGGL((k_level_wave<32, MODE_DECIDE>), grid, block, ldsw, s, as);
+            else hipLaunchKernelGGL((k_level_wave<32, MODE_FULLP>), grid, block, ldsw, s, as);
+        }
+    } else if (h->tgroup && use_screen32(h, d)) {
+        if (h->nblk) {   // compact node blocks: the sweep stages them instead of gathering C
+            // built transposed, as LDS images (C's rows staged in LDS), when a row fits
+            const size_t tl = sizeof(double) * (size_t)h->n + sizeof(uint64_t) * (size_t)h->W +
+                              (size_t)(h->maxdeg + 1) * (sizeof(int64_t) + 3 * sizeof(int));
+            if (h->nimg)
+                hipLaunchKernelGGL(k_node_blocks_t, dim3((unsigned)h->n), dim3(256), tl, s, as, s_lo, s_hi, (int)h->maxdeg);
+            else
+                hipLaunchKernelGGL(k_node_blocks, dim3((unsigned)h->n), dim3(256), 0, s, as, s_lo, s_hi);
+        }
+        as.lds_btab_off = (int)lds_f32_core(dl, 8);
+        if (h->nlpt && s_lo == 0 && s_hi == h->total_small) {   // the whole class: largest degree first
+            as.nps = reinterpret_cast<const int32_t *>((const int64_t *)h->cpre.p + h->lpt_off);
+            as.nord = as.nps + h->nlpt + 1;
+            as.nm = h->nlpt;
+        }
+        launch_lds_f<false>(d, (h->flags & PCG_FLAG_RECORD) != 0, nb, lds_tgroup_f_bytes(dl, d, 8), s, as);
+    } else if (h->tgroup) launch_lds_t<false>(d, nb, lds, s, as);
+    else if (mode == MODE_DECIDE) launch_lds_mode<MODE_DECIDE>(s, as, nb, lds);
+    else if (mode == MODE_FULLP) launch_lds_mode<MODE_FULLP>(s, as, nb, lds);
+    else launch_lds_mode<MODE_EXACT>(s, as, nb, lds);
+}
+
+// the wide class (the T-group kernels with 128-bit masks), chunks [w_lo, w_hi) of it, and the large
+// class (staged generic kernels), chunks [l_lo, l_hi) of it
+int run_wide_large(pcg_handle *h, const LevelArgs &a, int mode, int64_t w_lo, int64_t w_hi, int64_t l_lo, int64_t l_hi,
+                   hipStream_t s) {
+    const int d = a.d;
+    if (w_hi > w_lo) {
+        LevelArgs aw = a;
+        aw.cpre = (const int64_t *)h->cpre.p + (h->n + 1);
+        aw.chunk_lo = w_lo;
+        aw.bs = 256;
+        aw.spl = h->spl_w;
+        const int dl = (h->maxdeg_wide + 3) & ~3;
+        if (use_screen32(h, d)) {
+            aw.lds_btab_off = (int)lds_f32_core(dl, 16);
+            launch_lds_f<true>(d, (h->flags & PCG_FLAG_RECORD) != 0, w_hi - w_lo, lds_tgroup_f_bytes(dl, d, 16), s, aw);
+        } else {
+            aw.lds_btab_off = (int)lds_small_core(dl, 16);
+            launch_lds_t<true>(d, w_hi - w_lo, lds_tgroup_bytes(dl, d, 16), s, aw);
+        }
+    }
+    if (l_hi <= l_lo) return PCG_OK;
+    LevelArgs al = a;
+    al.cpre = (const int64_t *)h->cpre.p + 2 * (h->n + 1);
+    al.chunk_lo = l_lo;
+    if (d > PCG_MAX_DEPTH) {
+        const int64_t nch_deep = l_hi - l_lo;
+        const int grid = (int)std::min<int64_t>(nch_deep, 512);
+        const int m = d + 2;
+        const size_t per = (size_t)(m * m + 2 * m + (d + 2));
+        if (!pcg_ensure(h, h->pr_scratch, sizeof(double) * per * 64 * grid))
+            return pcg_fail(h, PCG_ERR_OOM, "deep-level scratch");
+        hipLaunchKernelGGL(k_level_deep, dim3(grid), dim3(64), 0, s, al, (double *)h->pr_scratch.p, nch_deep);
+        return PCG_OK;
+    }
+    const size_t lds = level_lds(h, al.bs);
+    if (lds > LDS_MAX) return pcg_fail(h, PCG_ERR_INVALID, "max degree %d too large for LDS staging", h->maxdeg);
+    if (mode == MODE_DECIDE && d == 1 && h->maxdeg <= L1_MAXD) {
+        const bool i32 = (int64_t)h->n * std::max<int64_t>(h->ldc, h->n) < ((int64_t)1 << 31);
+        const dim3 grid((unsigned)(l_hi - l_lo)), block(256);
+        if (i32) hipLaunchKernelGGL(k_level1_pairs<true>, grid, block, l1_lds_bytes(h->maxdeg), s, al);
+        else hipLaunchKernelGGL(k_level1_pairs<false>, grid, block, l1_lds_bytes(h->maxdeg), s, al);
+    } else if (mode == MODE_DECIDE) launch_level_mode<MODE_DECIDE>(s, al, l_hi - l_lo, lds);
+    else if (mode == MODE_FULLP) launch_level_mode<MODE_FULLP>(s, al, l_hi - l_lo, lds);
+    else launch_level_mode<MODE_EXACT>(s, al, l_hi - l_lo, lds);
+    return PCG_OK;
+}
+
+// A depth's node classes over chunks [chunk_lo, chunk_hi) of the level. With narrow and (wide or
+// large) chunks both present the two run side by side, forked after everything already on the main
+// stream and joined before the exact path. The class expected to finish first runs on the aux stream
+// (PCG_REST_MAIN: the depths whose wide / large class is the longer one run it on the main stream and
+// the narrow class on aux), so the join waits on an event that has usually fired already instead
+// of one that fires a cross-stream hop late. The order of the launches is fixed by two facts:
+//   1. the class on the main stream, the longer one, is launched first;
+//   2. the aux stream's wait on the fork point is enqueued after that launch, so the wait's host
+//      cost lands behind a kernel that is already running.
+// bracket_start: the kernel bracket's start event when the bracket is timed (it is the fork point,
+// already recorded on the main stream behind the prefix copy), else null: h->ev_fork is recorded here.
+int run_classes(pcg_handle *h, const LevelArgs &a, int mode, int64_t chunk_lo, int64_t chunk_hi, hipEvent_t bracket_start) {
+    const int64_t S = h->total_small, Wd = h->total_wide;
+    const int64_t s_lo = chunk_lo, s_hi = std::min(chunk_hi, S);
+    const int64_t w_lo = std::max(chunk_lo, S) - S, w_hi = std::max(std::min(chunk_hi, S + Wd) - S, w_lo);
+    const int64_t l_lo = std::max(chunk_lo, S + Wd) - (S + Wd);
+    const int64_t l_hi = std::max(chunk_hi - (S + Wd), l_lo);
+    const bool fork = s_hi > s_lo && (w_hi > w_lo || l_hi > l_lo);
+    const bool rest_main = fork && ((PCG_REST_MAIN >> a.d) & 1);
+    hipEvent_t fork_ev = bracket_start;
+    if (fork) {
+        if (!h->aux) PCG_HIP(h, hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
+        if (!h->ev_join) PCG_HIP(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
+        if (!fork_ev) {   // the fork point (no timing)
+            if (!h->ev_fork) PCG_HIP(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+            PCG_HIP(h, hipEventRecord(h->ev_fork, h->stream));
+            fork_ev = h->ev_fork;
+        }
+    }
+    const hipStream_t s_narrow = rest_main ? h->aux : h->stream;
+    const hipStream_t s_rest = fork && !rest_main ? h->aux : h->stream;
+    PCG_HT(h, "run:forked");
+    int rc = PCG_OK;
+    if (rest_main) rc = run_wide_large(h, a, mode, w_lo, w_hi, l_lo, l_hi, s_rest);
+    else run_narrow(h, a, mode, s_lo, s_hi, s_narrow);
+    PCG_HT(h, "run:first-class");
+    if (fork && !rc) PCG_HIP(h, hipStreamWaitEvent(h->aux, fork_ev, 0));
+    if (rest_main && !rc) run_narrow(h, a, mode, s_lo, s_hi, s_narrow);
+    else if (!rc) rc = run_wide_large(h, a, mode, w_lo, w_hi, l_lo, l_hi, s_rest);
+    if (rc) return rc;
+    PCG_HT(h, "run:second-class");
+    if (fork) {
+        PCG_HIP(h, hipEventRecord(h->ev_join, h->aux));
+        PCG_HIP(h, hipStreamWaitEvent(h->stream, h->ev_join, 0));
+    }
+    return PCG_OK;
+}
+
+// the level's tail behind the classes (depths <= PCG_MAX_DEPTH): the fp32 sweep's undecided tests in
+// fp64, then the exact path over the deferred list. The kernels read the lists' lengths on the
+// device (no host round trip) and raise the overflow status byte if a list overflowed.
+// stamp_end: the first kernel here closes the kernel bracket with a device wall-clock stamp
+int run_level_tail(pcg_handle *h, int d, int mode, bool stamp_end, hipStream_t s) {
+    LevelArgs a = make_args(h, d, mode == MODE_EXACT);
+    a.stamp_end = stamp_end ? 1 : 0;
+    const bool rec = (h->flags & PCG_FLAG_RECORD) != 0;
+    const bool screened = h->tgroup && use_screen32(h, d);
+    if (screened && !rec) {
+        // the screen and the exact path in one launch (k_screen_exact)
+        with_int<2, 4>(d, [&](auto dm) { hipLaunchKernelGGL(k_screen_exact<decltype(dm)::value>, dim3(256), dim3(256), 0, s, a); });
+        PCG_HIP(h, hipGetLastError());
+        return PCG_OK;
+    }
+    if (screened) {
+        // the list length is only known on the device; a grid-stride loop over it (1024 blocks
+        // measured no faster than 256: 40 vs 36 us for 1.3e5 tests)
+        with_int<2, 4>(d, [&](auto dm) { hipLaunchKernelGGL(k_screen<decltype(dm)::value>, dim3(256), dim3(256), 0, s, a); });
+        a.stamp_end = 0;
+    }
+    const int m = d + 2;
+    const int per = (m * m + 2 * m) * 8;      // one LDS slot per wave
+    // records: every test of a recorded pair comes here (up to ~1e6 at config 5 depth 4 with a
+    // 1-in-4099 pair sample), a lane each at d <= 4; otherwise the threshold mode's few band
+    // tests, a wave each
+    if (rec && m <= 6)
+        with_int<2, 6>(m, [&](auto mm) { hipLaunchKernelGGL(k_exact_lanes<decltype(mm)::value>, dim3(1024), dim3(256), 0, s, a); });
+    else
+        hipLaunchKernelGGL(k_exact, dim3(256), dim3(256), (size_t)per * 4, s, a);
+    PCG_HIP(h, hipGetLastError());
+    return PCG_OK;
+}
+
+}  // namespace
+
 extern "C" int pcg_level_run(pcg_handle *h, int64_t chunk_lo, int64_t chunk_hi) {
     if (!h || chunk_lo < 0 || chunk_hi > h->total_chunks || chunk_lo > chunk_hi)
         return pcg_fail(h, PCG_ERR_INVALID, "pcg_level_run: chunk range");
     const int d = h->depth;
     const int mode = mode_of(h, d);
-    const bool rec = (h->flags & PCG_FLAG_RECORD) != 0;   // T-group sweeps with record routing
     PCG_HT(h, "run:start");
-    {
-        LevelArgs a = make_args(h, d, mode == MODE_EXACT);
-        a.chunk_lo = chunk_lo;
-        const int64_t nch = chunk_hi - chunk_lo;
-        hipEvent_t *rv = h->rev[d];
-        // kernel bracket: timing events, or (skeleton_once) the prefix copy's and the first
-        // post-class kernel's wall-clock stamps
-        const bool kb = !h->stamps || d > PCG_MAX_DEPTH;
-        for (int k = 0; k < 2; ++k)
-            if (!rv[k]) PCG_HIP(h, hipEventCreate(&rv[k]));
-        if (kb) PCG_HIP(h, hipEventRecord(rv[0], h->stream));
-        if (nch > 0) {
-            if (d == 0) {
-                const dim3 grid((unsigned)nch), block(256);
-                if (mode == MODE_DECIDE) hipLaunchKernelGGL(k_level0<MODE_DECIDE>, grid, block, 0, h->stream, a);
-                else if (mode == MODE_FULLP) hipLaunchKernelGGL(k_level0<MODE_FULLP>, grid, block, 0, h->stream, a);
-                else hipLaunchKernelGGL(k_level0<MODE_EXACT>, grid, block, 0, h->stream, a);
-                if (h->banned && chunk_lo == 0) {
-                    // background knowledge (pcg_set_forbidden_pairs): pairs forbidden in both
-                    // directions leave at the end of depth 0 whatever their tests said
-                    // (SkeletonDiscovery.py:86-101, stable branch). Rank 0's slice carries them
-                    // into the merged flags in a sharded run.
-                    const int64_t nn = (int64_t)h->n * h->n;
-                    hipLaunchKernelGGL(k_or_flags, dim3((unsigned)std::min<int64_t>((nn + 255) / 256, 4096)), dim3(256), 0,
-                                       h->stream, h->banned, (int64_t)h->n, a.rm);
-                }
-            } else if (l1z_use(h, d) && chunk_lo == 0 && chunk_hi == h->total_chunks) {
-                // the whole depth by conditioning node (k_level1_z)
-                if (!h->l1z_pre)
-                    if (int rc = l1z_edges(h)) return rc;
-                const int64_t S1 = std::max<int64_t>(h->sumdeg, 1);
-                const double *cxe = (const double *)h->cblk.p, *dte = cxe + S1;
-                hipLaunchKernelGGL(k_level1_z, dim3((unsigned)h->n), dim3(L1Z_BS), l1z_lds_bytes(h->n, h->W, h->maxdeg), h->stream,
-                                   a, cxe, dte);
-            } else {
-                const int64_t S = h->total_small, Wd = h->total_wide;
-                const int64_t s_lo = chunk_lo, s_hi = std::min(chunk_hi, S);
-                const int64_t w_lo = std::max(chunk_lo, S) - S, w_hi = std::max(std::min(chunk_hi, S + Wd) - S, w_lo);
-                const int64_t l_lo = std::max(chunk_lo, S + Wd) - (S + Wd);
-                const int64_t l_hi = std::max(chunk_hi - (S + Wd), l_lo);
-                // narrow and (wide or large) present: the wide / large classes run on the aux
-                // stream beside the narrow class, forked after everything already on the main
-                // stream and joined before the exact path
-                // PCG_CLASS_ORDER (A/B): 0 narrow launched first, the wide / large classes forked
-                // beside it; 1 the same with the wide / large launches first; 2 / 3 no fork (one
-                // stream: narrow then the rest / the rest then narrow)
-                const bool fork = PCG_CLASS_ORDER <= 1 && s_hi > s_lo && (w_hi > w_lo || l_hi > l_lo);
-                hipStream_t main_stream = h->stream;
-                // the fork point is the kernel bracket's start event rv[0] (or ev_fork), recorded on the
-                // main stream after the prefix copy. The class expected to finish first runs on the aux
-                // stream (PCG_REST_MAIN: depths whose wide / large class is the longer one run it on
-                // the main stream and the narrow class on aux), so the join waits on an event that has
-                // usually fired already instead of one that fires a cross-stream hop late
-                const bool rest_main = fork && ((PCG_REST_MAIN >> d) & 1);
-                if (fork) {
-                    if (!h->aux) PCG_HIP(h, hipStreamCreateWithFlags(&h->aux, hipStreamNonBlocking));
-                    if (!h->ev_join) PCG_HIP(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-                    if (!kb) {   // the fork point (no timing)
-                        if (!h->ev_fork) PCG_HIP(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-                        PCG_HIP(h, hipEventRecord(h->ev_fork, h->stream));
-                    }
-                }
-                auto run_narrow = [&]() -> int {
-                    if (s_hi > s_lo) {
-                        LevelArgs as = a;
-                        as.chunk_lo = s_lo;
-                        as.bs = 256;
-                        const int dl = h->tgroup ? (h->maxdeg_small + 3) & ~3 : h->maxdeg_small;
-                        as.lds_btab_off = (int)lds_small_core(dl);
-                        size_t lds = h->tgroup ? lds_tgroup_bytes(dl, d) : lds_small_bytes(dl);
-                        if (!h->tgroup && d > PCG_MAX_DEPTH)   // k_level_lds's per-wave exact-path slots
-                            lds = std::max(lds, lds_small_core(dl) + 4 * sizeof(double) * WAVE_SLOT_DOUBLES(PCG_LDS_DEEP_TOP));
-                        if (h->wavek) {
-                            const dim3 grid((unsigned)(s_hi - s_lo)), block(256);
-                            const size_t core = lds_small_core(h->maxdeg_small);
-                            as.lds_btab_off = (int)core;
-                            if (d <= 16) {
-                                const size_t ldsw = core + 4 * sizeof(double) * (WAVE_SLOT_DOUBLES(16) + 16);
-                                if (mode == MODE_DECIDE) hipLaunchKernelGGL((k_level_wave<16, MODE_DECIDE>), grid, block, ldsw, h->stream, as);
-                                else hipLaunchKernelGGL((k_level_wave<16, MODE_FULLP>), grid, block, ldsw, h->stream, as);
-                            } else {
-                                const size_t ldsw = core + 4 * sizeof(double) * (WAVE_SLOT_DOUBLES(32) + 32);
-                                if (mode == MODE_DECIDE) hipLaunchKernelGGL((k_level_wave<32, MODE_DECIDE>), grid, block, ldsw, h->stream, as);
-                                else hipLaunchKernelGGL((k_level_wave<32, MODE_FULLP>), grid, block, ldsw, h->stream, as);
-                            }
-                        } else if (h->tgroup && use_screen32(h, d)) {
-                            if (h->nblk) {   // compact node blocks: the sweep stages them instead of gathering C
-                                // built transposed (C's rows staged in LDS) when a row fits
-                                const size_t tl = sizeof(double) * (size_t)h->n + sizeof(uint64_t) * (size_t)h->W +
-                                                  (size_t)(h->maxdeg + 1) * (sizeof(int64_t) + 3 * sizeof(int));
-                                if (h->nimg)
-                                    hipLaunchKernelGGL(k_node_blocks_t<true>, dim3((unsigned)h->n), dim3(256), tl, h->stream, as, s_lo,
-                                                       s_hi, (int)h->maxdeg);
-                                else if (PCG_NBLK_T && tl <= 64 * 1024)
-                                    hipLaunchKernelGGL(k_node_blocks_t<false>, dim3((unsigned)h->n), dim3(256), tl, h->stream, as, s_lo,
-                                                       s_hi, (int)h->maxdeg);
-                                else
-                                    hipLaunchKernelGGL(k_node_blocks, dim3((unsigned)h->n), dim3(256), 0, h->stream, as, s_lo, s_hi);
-                            }
-                            as.lds_btab_off = (int)lds_f32_core(dl, 8);
-                            const size_t ldsf = lds_tgroup_f_bytes(dl, d, 8);
-                            const dim3 grid((unsigned)(s_hi - s_lo)), block(256);
-                            if (h->nlpt && s_lo == 0 && s_hi == S) {   // the whole class: largest degree first
-                                as.nps = reinterpret_cast<const int32_t *>((const int64_t *)h->cpre.p + h->lpt_off);
-                                as.nord = as.nps + h->nlpt + 1;
-                                as.nm = h->nlpt;
-                            }
-                            if (d == 2) { if (rec) hipLaunchKernelGGL((k_level_lds_f<2, false, true>), grid, block, ldsf, h->stream, as); else hipLaunchKernelGGL((k_level_lds_f<2, false>), grid, block, ldsf, h->stream, as); }
-                            else if (d == 3) { if (rec) hipLaunchKernelGGL((k_level_lds_f<3, false, true>), grid, block, ldsf, h->stream, as); else hipLaunchKernelGGL((k_level_lds_f<3, false>), grid, block, ldsf, h->stream, as); }
-                            else { if (rec) hipLaunchKernelGGL((k_level_lds_f<4, false, true>), grid, block, ldsf, h->stream, as); else hipLaunchKernelGGL((k_level_lds_f<4, false>), grid, block, ldsf, h->stream, as); }
-                        } else if (h->tgroup) {
-                            const dim3 grid((unsigned)(s_hi - s_lo)), block(256);
-                            if (d == 2) hipLaunchKernelGGL((k_level_lds_t<2, false>), grid, block, lds, h->stream, as);
-                            else if (d == 3) hipLaunchKernelGGL((k_level_lds_t<3, false>), grid, block, lds, h->stream, as);
-                            else hipLaunchKernelGGL((k_level_lds_t<4, false>), grid, block, lds, h->stream, as);
-                        } else if (mode == MODE_DECIDE) launch_lds_mode<MODE_DECIDE>(h, as, s_hi - s_lo, lds);
-                        else if (mode == MODE_FULLP) launch_lds_mode<MODE_FULLP>(h, as, s_hi - s_lo, lds);
-                        else launch_lds_mode<MODE_EXACT>(h, as, s_hi - s_lo, lds);
-                    }
-                    return PCG_OK;
-                };
-                auto run_rest = [&]() -> int {
-                    if (w_hi > w_lo) {
-                        LevelArgs aw = a;
-                        aw.cpre = (const int64_t *)h->cpre.p + (h->n + 1);
-                        aw.chunk_lo = w_lo;
-                        aw.bs = 256;
-                        aw.spl = h->spl_w;
-                        const int dl = (h->maxdeg_wide + 3) & ~3;
-                        const dim3 grid((unsigned)(w_hi - w_lo)), block(256);
-                        if (use_screen32(h, d)) {
-                            aw.lds_btab_off = (int)lds_f32_core(dl, 16);
-                            const size_t lds = lds_tgroup_f_bytes(dl, d, 16);
-                            if (d == 2) { if (rec) hipLaunchKernelGGL((k_level_lds_f<2, true, true>), grid, block, lds, h->stream, aw); else hipLaunchKernelGGL((k_level_lds_f<2, true>), grid, block, lds, h->stream, aw); }
-                            else if (d == 3) { if (rec) hipLaunchKernelGGL((k_level_lds_f<3, true, true>), grid, block, lds, h->stream, aw); else hipLaunchKernelGGL((k_level_lds_f<3, true>), grid, block, lds, h->stream, aw); }
-                            else { if (rec) hipLaunchKernelGGL((k_level_lds_f<4, true, true>), grid, block, lds, h->stream, aw); else hipLaunchKernelGGL((k_level_lds_f<4, true>), grid, block, lds, h->stream, aw); }
-                        } else {
-                            aw.lds_btab_off = (int)lds_small_core(dl, 16);
-                            const size_t lds = lds_tgroup_bytes(dl, d, 16);
-                            if (d == 2) hipLaunchKernelGGL((k_level_lds_t<2, true>), grid, block, lds, h->stream, aw);
-                            else if (d == 3) hipLaunchKernelGGL((k_level_lds_t<3, true>), grid, block, lds, h->stream, aw);
-                            else hipLaunchKernelGGL((k_level_lds_t<4, true>), grid, block, lds, h->stream, aw);
-                        }
-                    }
-                    if (l_hi > l_lo && d > PCG_MAX_DEPTH) {
-                        LevelArgs al = a;
-                        al.cpre = (const int64_t *)h->cpre.p + 2 * (h->n + 1);
-                        const int64_t nch_deep = l_hi - l_lo;
-                        const int grid = (int)std::min<int64_t>(nch_deep, 512);
-                        const int m = d + 2;
-                        const size_t per = (size_t)(m * m + 2 * m + (d + 2));
-                        if (!pcg_ensure(h, h->pr_scratch, sizeof(double) * per * 64 * grid))
-                            return pcg_fail(h, PCG_ERR_OOM, "deep-level scratch");
-                        al.chunk_lo = l_lo;
-                        hipLaunchKernelGGL(k_level_deep, dim3(grid), dim3(64), 0, h->stream, al, (double *)h->pr_scratch.p,
-                                           nch_deep);
-                    } else if (l_hi > l_lo) {
-                        LevelArgs al = a;
-                        al.cpre = (const int64_t *)h->cpre.p + 2 * (h->n + 1);
-                        al.chunk_lo = l_lo;
-                        const size_t lds = level_lds(h, al.bs);
-                        if (lds > LDS_MAX)
-                            return pcg_fail(h, PCG_ERR_INVALID, "max degree %d too large for LDS staging", h->maxdeg);
-                        if (mode == MODE_DECIDE && d == 1 && h->maxdeg <= L1_MAXD)
-                        {
-                            const bool i32 = (int64_t)h->n * std::max<int64_t>(h->ldc, h->n) < ((int64_t)1 << 31);
-                            if (i32)
-                                hipLaunchKernelGGL(k_level1_pairs<true>, dim3((unsigned)(l_hi - l_lo)), dim3(256),
-                                                   l1_lds_bytes(h->maxdeg), h->stream, al);
-                            else
-                                hipLaunchKernelGGL(k_level1_pairs<false>, dim3((unsigned)(l_hi - l_lo)), dim3(256),
-                                                   l1_lds_bytes(h->maxdeg), h->stream, al);
-                        }
-                        else if (mode == MODE_DECIDE) launch_level_mode<MODE_DECIDE>(h, al, l_hi - l_lo, lds);
-                        else if (mode == MODE_FULLP) launch_level_mode<MODE_FULLP>(h, al, l_hi - l_lo, lds);
-                        else launch_level_mode<MODE_EXACT>(h, al, l_hi - l_lo, lds);
-                    }
-                    return PCG_OK;
-                };
-                // a class launched on the aux stream (h->stream swapped; restored on every exit)
-                auto launch = [&](bool on_aux, auto &&fn) -> int {
-                    struct StreamSwap {
-                        pcg_handle *h; hipStream_t main; bool on;
-                        ~StreamSwap() { if (on) h->stream = main; }
-                    } swap{h, main_stream, on_aux};
-                    if (on_aux) h->stream = h->aux;
-                    return fn();
-                };
-                // (the class on the main stream is launched first: it is the longer one)
-                const bool rest_first = PCG_CLASS_ORDER == 1 || PCG_CLASS_ORDER == 3 || (PCG_MAIN_FIRST && rest_main);
-                const bool narrow_aux = fork && rest_main, rest_aux = fork && !rest_main;
-                // the aux stream's wait on the fork point is enqueued after the main stream's first
-                // launch when that class runs on the main stream (PCG_FORK_LATE): the wait's host
-                // cost then lands behind a kernel that is already running
-                const bool late = PCG_FORK_LATE && fork && !(rest_first ? rest_aux : narrow_aux);
-                if (fork && !late) PCG_HIP(h, hipStreamWaitEvent(h->aux, kb ? rv[0] : h->ev_fork, 0));
-                PCG_HT(h, "run:forked");
-                int rc2 = rest_first ? launch(rest_aux, run_rest) : launch(narrow_aux, run_narrow);
-                PCG_HT(h, "run:first-class");
-                if (late && !rc2) PCG_HIP(h, hipStreamWaitEvent(h->aux, kb ? rv[0] : h->ev_fork, 0));
-                if (!rc2) rc2 = rest_first ? launch(narrow_aux, run_narrow) : launch(rest_aux, run_rest);
-                if (rc2) return rc2;
-                PCG_HT(h, "run:second-class");
-                if (fork) {
-                    PCG_HIP(h, hipEventRecord(h->ev_join, h->aux));
-                    PCG_HIP(h, hipStreamWaitEvent(main_stream, h->ev_join, 0));
-                }
-            }
-        }
-        PCG_HIP(h, hipGetLastError());
-        if (kb) PCG_HIP(h, hipEventRecord(rv[1], h->stream));
-        h->run_timed = kb;
-        PCG_HT(h, "run:launched");
-        // exact path over the deferred list; the kernel reads the list length on the device
-        // (no host round trip) and raises the overflow status byte if the list overflowed
-        // beyond PCG_MAX_DEPTH every kernel decides its band tests itself (k_level_wave,
-        // k_level_lds's wave slots, k_level_deep): nothing is deferred, no launch
-        if (d > PCG_MAX_DEPTH) return PCG_OK;
-        a = make_args(h, d, mode == MODE_EXACT);
-        a.stamp_end = kb ? 0 : 1;     // the first kernel behind the classes closes the bracket
-        if (PCG_SCREEN_EXACT && h->tgroup && use_screen32(h, d) && !(h->flags & PCG_FLAG_RECORD)) {
-            // the screen and the exact path in one launch (k_screen_exact)
-            if (d == 2) hipLaunchKernelGGL(k_screen_exact<2>, dim3(256), dim3(256), 0, h->stream, a);
-            else if (d == 3) hipLaunchKernelGGL(k_screen_exact<3>, dim3(256), dim3(256), 0, h->stream, a);
-            else hipLaunchKernelGGL(k_screen_exact<4>, dim3(256), dim3(256), 0, h->stream, a);
-            PCG_HIP(h, hipGetLastError());
-            return PCG_OK;
-        }
-        if (h->tgroup && use_screen32(h, d)) {   // the fp32 sweep's undecided tests, in fp64
-            // the list length is only known on the device; a grid-stride loop over it (1024 blocks
-            // measured no faster than 256: 40 vs 36 us for 1.3e5 tests)
-            if (d == 2) hipLaunchKernelGGL(k_screen<2>, dim3(256), dim3(256), 0, h->stream, a);
-            else if (d == 3) hipLaunchKernelGGL(k_screen<3>, dim3(256), dim3(256), 0, h->stream, a);
-            else hipLaunchKernelGGL(k_screen<4>, dim3(256), dim3(256), 0, h->stream, a);
-            a.stamp_end = 0;
-        }
-        const int m = d + 2;
-        const int per = (m * m + 2 * m) * 8;      // one LDS slot per wave
-        // records: every test of a recorded pair comes here (up to ~1e6 at config 5 depth 4 with a
-        // 1-in-4099 pair sample), a lane each at d <= 4; otherwise the threshold mode's few band
-        // tests, a wave each
-        if ((h->flags & PCG_FLAG_RECORD) && m <= 6) {
-            const dim3 g(1024), b(256);
-            if (m == 2) hipLaunchKernelGGL(k_exact_lanes<2>, g, b, 0, h->stream, a);
-            else if (m == 3) hipLaunchKernelGGL(k_exact_lanes<3>, g, b, 0, h->stream, a);
-            else if (m == 4) hipLaunchKernelGGL(k_exact_lanes<4>, g, b, 0, h->stream, a);
-            else if (m == 5) hipLaunchKernelGGL(k_exact_lanes<5>, g, b, 0, h->stream, a);
-            else hipLaunchKernelGGL(k_exact_lanes<6>, g, b, 0, h->stream, a);
-        } else {
-            hipLaunchKernelGGL(k_exact, dim3(256), dim3(256), (size_t)per * 4, h->stream, a);
-        }
-        PCG_HIP(h, hipGetLastError());
-        return PCG_OK;
+    LevelArgs a = make_args(h, d, mode == MODE_EXACT);
+    a.chunk_lo = chunk_lo;
+    hipEvent_t *rv = h->rev[d];
+    // kernel bracket: timing events, or (the level loop, h->stamps) the prefix copy's and the first
+    // post-class kernel's wall-clock stamps
+    const bool kb = !h->stamps || d > PCG_MAX_DEPTH;
+    for (int k = 0; k < 2; ++k)
+        if (!rv[k]) PCG_HIP(h, hipEventCreate(&rv[k]));
+    if (kb) PCG_HIP(h, hipEventRecord(rv[0], h->stream));
+    if (chunk_hi > chunk_lo) {
+        int rc = PCG_OK;
+        if (d == 0) run_depth0(h, a, mode, chunk_hi - chunk_lo, h->stream);
+        else if (l1z_use(h, d) && chunk_lo == 0 && chunk_hi == h->total_chunks) rc = run_depth1_z(h, a, h->stream);
+        else rc = run_classes(h, a, mode, chunk_lo, chunk_hi, kb ? rv[0] : nullptr);
+        if (rc) return rc;
     }
+    PCG_HIP(h, hipGetLastError());
+    if (kb) PCG_HIP(h, hipEventRecord(rv[1], h->stream));
+    h->run_timed = kb;
+    PCG_HT(h, "run:launched");
+    // beyond PCG_MAX_DEPTH every kernel decides its band tests itself (k_level_wave,
+    // k_level_lds's wave slots, k_level_deep): nothing is deferred, no launch
+    if (d > PCG_MAX_DEPTH) return PCG_OK;
+    return run_level_tail(h, d, mode, !kb, h->stream);
 }
 
 // the level barrier of the current depth, enqueued: removals applied, the next graph's summary and
@@ -5967,7 +5736,7 @@ int level_end_enqueue(pcg_handle *h, unsigned long long *seq) {
     // graphs whose CSR holds at most PCG_TUNE_EXPORT_INLINE entries export on the handle's stream
     // the last depth of a max_depth-bounded run has no next depth to overlap its export with: it
     // runs right behind the barrier on the handle's stream (no cross-stream hop before the sync)
-    const bool last = PCG_LAST_XINL && h->run_max_depth >= 0 && d >= h->run_max_depth;
+    const bool last = h->run_max_depth >= 0 && d >= h->run_max_depth;
     if (!rc && d >= 1 && xsum > 0 && (last || xsum <= h->tune[PCG_TUNE_EXPORT_INLINE])) {
         // a small graph's export on the handle's stream, right behind the barrier: one launch
         // instead of the export stream's four calls (it runs while the host decomposes the next
@@ -6043,7 +5812,6 @@ int level_end_finish(pcg_handle *h, int d, unsigned long long seq, pcg_stats *st
     // the device's near-alpha list accumulates over the run: this depth's entries follow the
     // ones already copied
     const int64_t near_cum = std::min<int64_t>((int64_t)c.near_alpha, h->near_cap);
-    h->near_pending = near_cum;
     if (!h->defer_near && near_cum > h->near_seen) {
         const size_t old = h->near_h.size();
         h->near_h.resize(old + (near_cum - h->near_seen));
@@ -6159,7 +5927,7 @@ extern "C" int pcg_level_end(pcg_handle *h, pcg_stats *stats) {
     return level_end_finish(h, h->depth, seq, stats);
 }
 
-// the level loop's tail (PCG_TAIL_SPIN): the exports still on the export stream joined into the
+// the level loop's tail: the exports still on the export stream joined into the
 // handle's stream, then k_tail_copy (queued right behind the last depth's barrier when the depth
 // bound says it is the last); the host spins on its sequence number as on a level summary
 static int tail_launch(pcg_handle *h) {
@@ -6231,13 +5999,13 @@ void level_run_begin(pcg_handle *h, int max_depth) {
     h->htrace.clear();
     PCG_HT(h, "init:start");
     h->lev_on = true;
-    h->lev_n = 0;
     h->defer_near = true;
-    h->near_pending = 0;
     h->run_max_depth = max_depth;
-    h->stamps = !PCG_KBRACKET;
+    // the loop's depth and kernel brackets are device wall-clock stamps in kernels already queued
+    // (timing events are each a ~6 us marker on the device's critical path: 4.21-4.24 -> 4.18-4.20 ms)
+    h->stamps = true;
     h->lev_stamp.clear();
-    if (h->stamps && h->wall_khz <= 0) {
+    if (h->wall_khz <= 0) {
         int khz = 0;
         (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, h->device);
         h->wall_khz = khz > 0 ? khz : 100000;
@@ -6246,7 +6014,7 @@ void level_run_begin(pcg_handle *h, int max_depth) {
 
 // the depth bound's last depth: the tail transfer is queued behind its barrier right away
 bool level_run_tail_early(const pcg_handle *h, int depth) {
-    return PCG_TAIL_SPIN && PCG_TAIL_EARLY && h->run_max_depth >= 0 && depth >= h->run_max_depth;
+    return h->run_max_depth >= 0 && depth >= h->run_max_depth;
 }
 
 int level_run_tail_launch(pcg_handle *h) { return tail_launch(h); }
@@ -6275,51 +6043,23 @@ int level_run_finish(pcg_handle *h, int done, bool tail_queued) {
     h->lev_on = false;
     h->defer_near = false;
     h->run_max_depth = -1;
-    const bool stamped = h->stamps;
     h->stamps = false;
-    const int64_t nnew = h->near_pending - h->near_seen;
-    if (PCG_TAIL_SPIN) {
-        if (!tail_queued) rc = tail_launch(h);
-        if (!rc) rc = tail_wait(h);
-        if (rc) return rc;
-    } else if (nnew > 0) {
-        if (!pcg_ensure_pinned(h, h->near_pin, sizeof(pcg_record) * (size_t)nnew))
-            return pcg_fail(h, PCG_ERR_OOM, "pinned near-alpha records");
-        PCG_HIP(h, hipMemcpyAsync(h->near_pin.p, (pcg_record *)h->nearbuf.p + h->near_seen,
-                                  sizeof(pcg_record) * (size_t)nnew, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (!PCG_TAIL_SPIN) rc = export_sync(h);   // the last depth's export (the skeleton's sepset rows)
+    // the last transfer: one kernel into host-coherent memory and a host spin (no blits, no sync)
+    if (!tail_queued) rc = tail_launch(h);
+    if (!rc) rc = tail_wait(h);
     if (rc) return rc;
-    if (!PCG_TAIL_SPIN && nnew > 0) {
-        PCG_HIP(h, hipStreamSynchronize(h->stream));
-        const pcg_record *src = (const pcg_record *)h->near_pin.p;
-        h->near_h.insert(h->near_h.end(), src, src + nnew);
-        h->near_seen = h->near_pending;
+    // (every caller came through level_run_begin: the depth boundaries are the summaries' stamps)
+    for (int depth = 0; depth < done && depth + 1 < (int)h->lev_stamp.size(); ++depth) {
+        const unsigned long long t0 = h->lev_stamp[depth], t1 = h->lev_stamp[depth + 1];
+        if (t0 && t1 > t0) h->st.level_ms[depth] = (double)(t1 - t0) / h->wall_khz;
     }
-    if (stamped) {
-        for (int depth = 0; depth < done && depth + 1 < (int)h->lev_stamp.size(); ++depth) {
-            const unsigned long long t0 = h->lev_stamp[depth], t1 = h->lev_stamp[depth + 1];
-            if (t0 && t1 > t0) h->st.level_ms[depth] = (double)(t1 - t0) / h->wall_khz;
-        }
-        for (int depth = PCG_MAX_DEPTH + 1; depth < done; ++depth)   // (unstamped depths: event brackets)
-            if (h->rev[depth][1]) {
-                float ms = 0.f;
-                PCG_HIP(h, hipEventSynchronize(h->rev[depth][1]));
-                PCG_HIP(h, hipEventElapsedTime(&ms, h->rev[depth][0], h->rev[depth][1]));
-                h->st.kernel_ms[depth] = ms;
-            }
-    } else if (done && h->lev_n > done) {
-        PCG_HIP(h, hipEventSynchronize(h->lev[done]));
-        for (int depth = 0; depth < done; ++depth) {
+    for (int depth = PCG_MAX_DEPTH + 1; depth < done; ++depth)   // (unstamped depths: event brackets)
+        if (h->rev[depth][1]) {
             float ms = 0.f;
-            PCG_HIP(h, hipEventElapsedTime(&ms, h->lev[depth], h->lev[depth + 1]));
-            h->st.level_ms[depth] = ms;
-            if (h->rev[depth][1]) {     // the CI-test kernel brackets, read here, off the per-depth path
-                PCG_HIP(h, hipEventElapsedTime(&ms, h->rev[depth][0], h->rev[depth][1]));
-                h->st.kernel_ms[depth] = ms;
-            }
+            PCG_HIP(h, hipEventSynchronize(h->rev[depth][1]));
+            PCG_HIP(h, hipEventElapsedTime(&ms, h->rev[depth][0], h->rev[depth][1]));
+            h->st.kernel_ms[depth] = ms;
         }
-    }
     if (h->htrace_on && !h->htrace.empty()) {
         const double t0 = h->htrace.front().second;
         double prev = t0;
@@ -6550,7 +6290,7 @@ int export_sync(pcg_handle *h) {
     // exports on the handle's stream (xinl) and/or on the export stream: the counter is read
     // behind all of them
     hipStream_t s = h->xs ? h->xs : h->stream;
-    if (PCG_LAST_XINL && h->xs && h->xinl) {
+    if (h->xs && h->xinl) {
         // the counter is read on the handle's stream, behind the export stream's pending exports
         for (int i = 0; i < 2; ++i)
             if (h->xpending[i]) PCG_HIP(h, hipStreamWaitEvent(h->stream, h->ev_xdone[i], 0));

@@ -235,6 +235,51 @@ int pcg_record_count(pcg_handle *h, int64_t *count, int64_t *near_alpha_count);
 int pcg_record_export(pcg_handle *h, pcg_record *rec_host, int64_t count,
                       pcg_record *near_host, int64_t near_count);
 
+/* ---- batched small graphs: many cases (2 <= n <= 64) in one launch ------------------
+ * The RQ2 workload is hundreds of independent cases of 30-49 metrics; bootstrap / stability
+ * selection PC is many resamples of one case. pcg_skeleton_batch runs the single-workgroup
+ * small-graph kernel with one workgroup per case (and, for cases given as data, one batched K1
+ * launch in front of it), and waits on the host once for the whole batch.
+ * cases: host array of `count` descriptors whose pointers are device memory, caller-owned.
+ * results: host array of `count`, filled on return.
+ * flags: PCG_FLAG_FULL_P and PCG_FLAG_EXACT_ALL only. PCG_FLAG_RECORD, a registered
+ * forbidden-pairs mask (pcg_set_forbidden_pairs), pcg_set_world_size != 1, a caller-owned
+ * removal buffer (pcg_set_removal_buffer) or a case with n outside 2..64 give PCG_ERR_INVALID
+ * before anything is launched. PCG_TUNE_SMALL is not consulted (the batch is the small kernel).
+ * The return value is non-zero only for a batch-level failure (invalid arguments, OOM, a HIP
+ * error). A singular / math-domain case reports it in its own results[i].rc and stats.error and
+ * leaves every other case untouched. A case the small kernel gives up on (deeper than its 16
+ * levels, or a full band queue) is rerun on the level loop after the batch, its rows copied into
+ * the case's own buffers, and reports PCG_DRIVER_SMALL_RERUN.
+ * All device work runs on the handle's stream and the call returns after the stream was
+ * synchronised: removed_level, the sepset rows and C are complete on return for a caller on any
+ * stream. The per-case near-alpha lists (at most 1024 records each) stay in the handle until the
+ * next pcg_skeleton_batch: pcg_batch_near_export copies the first `count` records of one case.
+ * The handle stays usable for any following call; pcg_degrees / pcg_sepset_* / pcg_record_*
+ * then describe an empty run (the batch's results are in `results` and the cases' buffers).  */
+typedef struct {                       /* one case, every pointer device memory              */
+    const double *X;                   /* N x n data, or NULL: C is then the input           */
+    int64_t N, n, ldx;                 /* samples, variables (2..64), leading dimension of X */
+    double *C;                         /* n x n correlation: written when X != NULL          */
+    int64_t ldc;
+    int8_t *removed_level;             /* n x n out                                          */
+    int32_t *sep_xy;                   /* out, 2 x n*(n-1) int32: (x, y) of each sepset row  */
+    uint64_t *sep_bits;                /* out, n*(n-1) rows of one word                      */
+} pcg_case;
+typedef struct {                       /* host memory, one per case                          */
+    int32_t rc;                        /* PCG_OK or this case's PCG_ERR_SINGULAR / _DOMAIN / ... */
+    int32_t rc_pad;
+    int64_t sep_rows;                  /* sepset rows written to sep_xy / sep_bits           */
+    int64_t near_alpha_count;          /* records pcg_batch_near_export can return           */
+    pcg_stats stats;                   /* stats.driver: PCG_DRIVER_SMALL or _SMALL_RERUN     */
+    int32_t deg[PCG_MAX_LEVELS][64];   /* degrees at the start of each depth (as pcg_degrees) */
+} pcg_case_result;
+int pcg_skeleton_batch(pcg_handle *h, const pcg_case *cases, int64_t count, double alpha,
+                       int max_depth, int flags, pcg_case_result *results);
+/* sizeof(pcg_case), sizeof(pcg_case_result) as the library was built (host only).          */
+int pcg_batch_abi_info(int64_t *case_bytes, int64_t *result_bytes);
+int pcg_batch_near_export(pcg_handle *h, int64_t case_index, pcg_record *rec_host, int64_t count);
+
 /* ---- multi-GPU level step (edge-sharded skeleton) ----------------------------------
  * The host drives the level loop: pcg_level_begin prepares depth d from the current
  * adjacency and returns the work size; pcg_level_run evaluates the chunk range

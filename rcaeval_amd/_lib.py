@@ -95,6 +95,18 @@ class PcgRecord(ctypes.Structure):
     _fields_ = [("a", I32), ("b", I32), ("d", I32), ("s", I32 * PCG_MAX_DEPTH), ("p", D)]
 
 
+class PcgCase(ctypes.Structure):
+    """pcg_case: one case of pcg_skeleton_batch (every pointer device memory)."""
+    _fields_ = [("X", P), ("N", I64), ("n", I64), ("ldx", I64), ("C", P), ("ldc", I64),
+                ("removed_level", P), ("sep_xy", P), ("sep_bits", P)]
+
+
+class PcgCaseResult(ctypes.Structure):
+    """pcg_case_result: one case's outcome of pcg_skeleton_batch (host memory)."""
+    _fields_ = [("rc", I32), ("rc_pad", I32), ("sep_rows", I64), ("near_alpha_count", I64),
+                ("stats", PcgStats), ("deg", (I32 * 64) * PCG_MAX_LEVELS)]
+
+
 # (name, restype, argtypes) — exactly the exports of include/pcgpu.h
 SIGNATURES = [
     ("pcg_abi_info", I32, [ctypes.POINTER(I64), ctypes.POINTER(I64), ctypes.POINTER(I32)]),
@@ -123,6 +135,10 @@ SIGNATURES = [
     ("pcg_sepset_target", I32, [P, ctypes.POINTER(I32), ctypes.POINTER(I64)]),
     ("pcg_record_count", I32, [P, ctypes.POINTER(I64), ctypes.POINTER(I64)]),
     ("pcg_record_export", I32, [P, P, I64, P, I64]),
+    ("pcg_skeleton_batch", I32, [P, ctypes.POINTER(PcgCase), I64, D, ctypes.c_int, ctypes.c_int,
+                                 ctypes.POINTER(PcgCaseResult)]),
+    ("pcg_batch_abi_info", I32, [ctypes.POINTER(I64), ctypes.POINTER(I64)]),
+    ("pcg_batch_near_export", I32, [P, I64, P, I64]),
     ("pcg_skeleton_init", I32, [P, P, I64, I64, I64, D, ctypes.c_int, P]),
     ("pcg_level_begin", I32, [P, ctypes.c_int, ctypes.POINTER(I64), ctypes.POINTER(I32), ctypes.POINTER(P)]),
     ("pcg_level_run", I32, [P, I64, I64]),
@@ -202,6 +218,13 @@ def check_abi(lib, stats_cls=None, record_cls=None) -> None:
         raise EngineUnavailable(
             f"{LIB_PATH}: ABI mismatch (library sizeof(pcg_stats)={sb}, sizeof(pcg_record)={rb}, "
             f"version {ver}; bindings {mine[0]}, {mine[1]}, version {mine[2]}): rebuild the library "
+            "or update rcaeval_amd/_lib.py with include/pcgpu.h")
+    cb, qb = I64(), I64()
+    lib.pcg_batch_abi_info(ctypes.byref(cb), ctypes.byref(qb))
+    if (cb.value, qb.value) != (ctypes.sizeof(PcgCase), ctypes.sizeof(PcgCaseResult)):
+        raise EngineUnavailable(
+            f"{LIB_PATH}: ABI mismatch (library sizeof(pcg_case)={cb.value}, sizeof(pcg_case_result)={qb.value}; "
+            f"bindings {ctypes.sizeof(PcgCase)}, {ctypes.sizeof(PcgCaseResult)}): rebuild the library "
             "or update rcaeval_amd/_lib.py with include/pcgpu.h")
 
 

@@ -372,3 +372,81 @@ def pc(data: np.ndarray, alpha: float = 0.05, indep_test=fisherz, stable: bool =
     cg = CausalGraph(graph, names, out, C=C, N=X.shape[0], alpha=alpha, device=device, banned=banned)
     cg.PC_elapsed = time.time() - start
     return cg
+
+
+_BATCH_DEFAULTS = {"indep_test": fisherz, "stable": True, "uc_rule": 0, "uc_priority": 2, "mvpc": False,
+                   "background_knowledge": None}
+
+
+def _check_batch_options(options: dict) -> None:
+    """pc_batch runs ``pc``'s default configuration only; anything else is refused before the
+    device is touched."""
+    for k, v in options.items():
+        if k not in _BATCH_DEFAULTS:
+            raise TypeError(f"pc_batch() got an unexpected keyword argument {k!r}")
+        want = _BATCH_DEFAULTS[k]
+        name = v if isinstance(v, str) or k != "indep_test" else getattr(v, "__name__", str(v))
+        same = (v is None) if k == "background_knowledge" else (name == want)
+        if not same:
+            raise NotImplementedError(f"pc_batch: {k}={v!r} (only pc's defaults run batched: fisherz, stable, "
+                                      "uc_rule 0, uc_priority 2, no background knowledge); call pc() per case")
+
+
+def pc_batch(datas, alpha: float = 0.05, node_names=None, max_depth: int = -1, device: int | None = None,
+             return_exceptions: bool = False, **options) -> list:
+    """``[pc(d) for d in datas]`` with the cases of 2..64 variables run together: one batched K1
+    launch, one batched skeleton launch and one host wait for all of them (``Engine.skeleton_batch``),
+    one device-to-host copy of every removal matrix and sepset row, then the host orientation per
+    case. Each element equals what ``pc(data, alpha, node_names=..., max_depth=...)`` returns for
+    that case. Cases outside 2..64 variables (or with fewer than 2 rows) and cases whose skeleton
+    reported an error are run through ``pc()`` itself, so sizes, errors and warnings behave as
+    they do there. ``node_names``: None, or one list (or None) per case.
+    ``return_exceptions=True`` returns a case's exception in its slot instead of raising it (the
+    default raises the first failing case's, in case order)."""
+    assert 0 < alpha < 1
+    _check_batch_options(options)
+    datas = list(datas)
+    if not datas:
+        return []
+    names_in = list(node_names) if node_names is not None else [None] * len(datas)
+    if len(names_in) != len(datas):
+        raise ValueError("pc_batch: node_names must hold one entry per case")
+    start = time.time()
+    results: list = [None] * len(datas)
+    batched = []
+    for i, data in enumerate(datas):
+        ok = (type(data) == np.ndarray and data.ndim == 2 and 2 <= data.shape[1] <= 64 and data.shape[0] >= 2)
+        if ok:
+            X = np.asarray(data, dtype=np.float64)
+            ok = not (np.isnan(X).any() or np.isinf(X).any())     # pc() raises its own assertion for these
+        if ok:
+            if data.shape[0] < data.shape[1]:
+                warnings.warn("The number of features is much larger than the sample size!")
+            batched.append((i, X))
+    outs = []
+    if batched:
+        eng = get_engine(device)
+        with phase("K1 + skeleton"):
+            outs = eng.skeleton_batch([X for _, X in batched], alpha=alpha, max_depth=max_depth, from_data=True)
+    elapsed = (time.time() - start) / max(len(batched), 1)
+    for (i, X), out in zip(batched, outs):
+        if out.rc != 0:
+            continue                                 # pc() below reports it as it does today
+        n = X.shape[1]
+        names = names_in[i] if names_in[i] is not None else [f"X{k + 1}" for k in range(n)]
+        t0 = time.time()
+        with phase("orientation"):
+            graph = orient(out.adj, out.sep_xy, out.sep_bits, priority=2).astype(int)
+        cg = CausalGraph(graph, names, out, C=out.extra["C"], N=X.shape[0], alpha=alpha, device=device)
+        cg.PC_elapsed = elapsed + (time.time() - t0)
+        results[i] = cg
+    for i, data in enumerate(datas):
+        if results[i] is not None:
+            continue
+        try:
+            results[i] = pc(data, alpha=alpha, node_names=names_in[i], max_depth=max_depth, device=device)
+        except Exception as e:      # noqa: BLE001 - handed to the caller in the case's slot, or raised below
+            if not return_exceptions:
+                raise
+            results[i] = e
+    return results

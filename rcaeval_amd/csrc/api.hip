@@ -70,6 +70,12 @@ extern "C" int pcg_abi_info(int64_t *stats_bytes, int64_t *record_bytes, int32_t
     return PCG_OK;
 }
 
+extern "C" int pcg_batch_abi_info(int64_t *case_bytes, int64_t *result_bytes) {
+    if (case_bytes) *case_bytes = (int64_t)sizeof(pcg_case);
+    if (result_bytes) *result_bytes = (int64_t)sizeof(pcg_case_result);
+    return PCG_OK;
+}
+
 namespace {
 struct TuneSpec {
     const char *env;
@@ -167,10 +173,11 @@ extern "C" int pcg_destroy(pcg_handle *h) {
                       &h->ug2[1], &h->exp_ctr, &h->cpre, &h->binom, &h->ctr,
                       &h->deferred, &h->screenq, &h->records, &h->nearbuf, &h->exportbuf, &h->export_xy, &h->diag,
                       &h->colmean, &h->pr_scratch, &h->batch_scratch, &h->chisq_scratch, &h->cblk, &h->lmk,
-                      &h->k1_digits, &h->small_sum};
+                      &h->k1_digits, &h->small_sum, &h->batch_up, &h->batch_sum, &h->batch_near};
     for (DevBuf *b : bufs)
         if (b->p) hipFree(b->p);
-    PinBuf *pins[] = {&h->ctr_pin, &h->deg_pin, &h->off_pin, &h->cpre_pin, &h->status_pin, &h->small_pin};
+    PinBuf *pins[] = {&h->ctr_pin, &h->deg_pin, &h->off_pin, &h->cpre_pin, &h->status_pin, &h->small_pin,
+                      &h->batch_up_pin, &h->batch_sum_pin};
     for (PinBuf *b : pins)
         if (b->p) hipHostFree(b->p);
     if (h->summary) hipHostFree(h->summary);

@@ -1655,6 +1655,140 @@ int pcg_corr_launch(pcg_handle *h, const double *X, int64_t N, int64_t n, int64_
     return PCG_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// K1 of many small cases (pcg_skeleton_batch, n <= 64): one workgroup per case instead of
+// pcg_corr_launch's five launches per case. Column means, centring, the upper-triangle Gram of the
+// centred columns and numpy's normalisation order ((g * scale) / sd_row) / sd_col, both triangles
+// written, clipped to [-1, 1] with NaN passing through (a constant or non-finite column gives
+// numpy's NaN row and column, diagonal included). The rows stream from global memory through a
+// CSB_ROWS-row LDS tile of centred values; each thread owns up to CSB_EPT (i, j) entries.
+// Numerics: every sum over the N rows is compensated — the mean by two-sum over CSB_SEG fixed row
+// segments combined in segment order, the dot products by Dot2 (fma for the product's rounding
+// error, two-sum for the accumulation) in row order — so the Gram is the correctly rounded sum up
+// to O(N u^2) and C stays within the project's K1 tolerance of np.corrcoef. The order is fixed by
+// (N, n) alone: a case's C does not depend on the batch size or on its position in the batch.
+namespace {
+constexpr int CSB_THREADS = 512;
+constexpr int CSB_N = 64;
+constexpr int CSB_ROWS = 32;
+constexpr int CSB_SEG = CSB_THREADS / CSB_N;
+constexpr int CSB_EPT = (CSB_N * (CSB_N + 1) / 2 + CSB_THREADS - 1) / CSB_THREADS;
+
+// s + e = a + b exactly (Knuth); contraction is off so no step is fused
+__device__ __forceinline__ void two_sum(double a, double b, double &s, double &e) {
+#pragma clang fp contract(off)
+    s = a + b;
+    const double bb = s - a;
+    e = (a - (s - bb)) + (b - bb);
+}
+
+__global__ __launch_bounds__(CSB_THREADS) void k_corr_small_batch(const CorrSmallCase *cases) {
+#pragma clang fp contract(off)
+    __shared__ double tile[CSB_ROWS][CSB_N];
+    __shared__ double ps[CSB_SEG][CSB_N], pc[CSB_SEG][CSB_N];
+    __shared__ double mean[CSB_N], sd[CSB_N];
+    const CorrSmallCase cs = cases[blockIdx.x];
+    const int n = cs.n, tid = threadIdx.x;
+    if (!cs.X || n < 1 || n > CSB_N) return;      // (uniform over the block) C is this case's input
+    const int64_t N = cs.N, ldx = cs.ldx;
+    const double *X = cs.X;
+    {   // column means: compensated partial sums of CSB_SEG row segments, combined in segment order
+        const int col = tid & (CSB_N - 1), seg = tid / CSB_N;
+        const int64_t per = (N + CSB_SEG - 1) / CSB_SEG;
+        const int64_t r0 = std::min<int64_t>(N, seg * per), r1 = std::min<int64_t>(N, r0 + per);
+        double s = 0.0, c = 0.0;
+        if (col < n) {
+#pragma unroll 4
+            for (int64_t t = r0; t < r1; ++t) {
+                double ns, e;
+                two_sum(s, X[t * ldx + col], ns, e);
+                s = ns;
+                c += e;
+            }
+        }
+        ps[seg][col] = s;
+        pc[seg][col] = c;
+    }
+    __syncthreads();
+    if (tid < n) {
+        double s = ps[0][tid], c = pc[0][tid];
+        for (int q = 1; q < CSB_SEG; ++q) {
+            double ns, e;
+            two_sum(s, ps[q][tid], ns, e);
+            s = ns;
+            c += e + pc[q][tid];
+        }
+        mean[tid] = (s + c) / (double)N;
+    }
+    // this thread's entries of the upper triangle (row-major over i, j >= i)
+    const int npairs = n * (n + 1) / 2;
+    int ei[CSB_EPT], ej[CSB_EPT];
+    bool live[CSB_EPT];
+    double s[CSB_EPT], c[CSB_EPT];
+#pragma unroll
+    for (int k = 0; k < CSB_EPT; ++k) {
+        const int e = tid + k * CSB_THREADS;
+        live[k] = e < npairs;
+        int i = 0, r = live[k] ? e : 0;
+        while (r >= n - i) { r -= n - i; ++i; }
+        ei[k] = i;
+        ej[k] = i + r;
+        s[k] = c[k] = 0.0;
+    }
+    for (int64_t t0 = 0; t0 < N; t0 += CSB_ROWS) {
+        const int tr = (int)std::min<int64_t>(CSB_ROWS, N - t0);
+        __syncthreads();              // the means are written / the previous tile was consumed
+        for (int e = tid; e < CSB_ROWS * CSB_N; e += CSB_THREADS) {
+            const int r = e / CSB_N, col = e % CSB_N;
+            tile[r][col] = (r < tr && col < n) ? X[(t0 + r) * ldx + col] - mean[col] : 0.0;
+        }
+        __syncthreads();
+        for (int r = 0; r < tr; ++r) {
+#pragma unroll
+            for (int k = 0; k < CSB_EPT; ++k) {
+                if (!live[k]) continue;
+                const double x = tile[r][ei[k]], y = tile[r][ej[k]];
+                const double p = x * y;
+                const double pe = fma(x, y, -p);
+                double ns, e;
+                two_sum(s[k], p, ns, e);
+                s[k] = ns;
+                c[k] += e + pe;
+            }
+        }
+    }
+    const double scale = 1.0 / (double)(N - 1);
+#pragma unroll
+    for (int k = 0; k < CSB_EPT; ++k) {
+        s[k] += c[k];
+        if (live[k] && ei[k] == ej[k]) sd[ei[k]] = sqrt(s[k] * scale);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < CSB_EPT; ++k) {
+        if (!live[k]) continue;
+        const int i = ei[k], j = ej[k];
+        const double g = s[k] * scale;
+        double v = g / sd[i];
+        v = v / sd[j];
+        cs.C[(int64_t)i * cs.ldc + j] = v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v);  // NaN passes through
+        if (i != j) {
+            double w = g / sd[j];
+            w = w / sd[i];
+            cs.C[(int64_t)j * cs.ldc + i] = w > 1.0 ? 1.0 : (w < -1.0 ? -1.0 : w);
+        }
+    }
+}
+}  // namespace
+
+int corr_small_batch_launch(pcg_handle *h, const CorrSmallCase *cases, int64_t count) {
+    if (!h || !cases || count < 1 || count > INT32_MAX)
+        return pcg_fail(h, PCG_ERR_INVALID, "batched K1: invalid arguments");
+    hipLaunchKernelGGL(k_corr_small_batch, dim3((unsigned)count), dim3(CSB_THREADS), 0, h->stream, cases);
+    PCG_HIP(h, hipGetLastError());
+    return PCG_OK;
+}
+
 extern "C" int pcg_corr(pcg_handle *h, const double *X, int64_t N, int64_t n, int64_t ldx, double *C,
                         int64_t ldc) {
     const int rc = pcg_corr_launch(h, X, N, n, ldx, C, ldc);

@@ -98,6 +98,13 @@ struct pcg_handle {
     PinBuf ctr_pin, deg_pin, off_pin, cpre_pin, status_pin;
     DevBuf small_sum;                // single-workgroup small-graph skeleton: summary + counters
     PinBuf small_pin;                // its host copy
+    // pcg_skeleton_batch: per-case slices of one allocation each. batch_up: the cases' kernel
+    // arguments, K1 descriptors and depth constants (one H2D copy from batch_up_pin); batch_sum:
+    // the summaries followed by the near-alpha / record counters (one memset, one D2H copy into
+    // batch_sum_pin); batch_near: the near-alpha lists
+    DevBuf batch_up, batch_sum, batch_near;
+    PinBuf batch_up_pin, batch_sum_pin;
+    std::vector<std::vector<pcg_record>> batch_near_h;   // per case, for pcg_batch_near_export
     std::vector<uint64_t> binom_h;   // host copy of the binomial table
     uint8_t *rm_ext = nullptr;       // caller-owned removal-flag buffer (multi-GPU)
     const uint8_t *banned = nullptr; // pcg_set_forbidden_pairs: n x n pairs removed at depth 0
@@ -206,6 +213,15 @@ void pcg_comm_release(pcg_handle *h);      // comm.hip: destroy the communicator
 // corr.hip: K1 queued on h->stream without the host sync of pcg_corr (pcg_pc_skeleton)
 int export_sync(pcg_handle *h);   // skeleton.hip: wait for the sepset exports, take their row count
 int pcg_corr_launch(pcg_handle *h, const double *X, int64_t N, int64_t n, int64_t ldx, double *C, int64_t ldc);
+// corr.hip: K1 of many small cases (n <= 64), one workgroup per descriptor, queued on h->stream;
+// descriptors with X == nullptr are skipped. `cases` is device memory
+struct CorrSmallCase {
+    const double *X;
+    double *C;
+    int64_t N, ldx, ldc;
+    int32_t n, pad;
+};
+int corr_small_batch_launch(pcg_handle *h, const CorrSmallCase *cases, int64_t count);
 int64_t k1_plan_signature(const pcg_handle *h, int64_t n, int64_t N);   // corr.hip: K1's plan, for cross-rank agreement
 // corr.hip: the native sharded K1's CRT path without host syncs (see corr.hip)
 int corr_shard_crt_prepare(pcg_handle *h, int64_t N, int64_t n, int world, bool *crt, int64_t *unit_bytes);

@@ -4261,7 +4261,9 @@ __device__ void small_set(const SmallArgs &a, const SmallDepth &kd, const double
     }
 }
 
-__global__ __launch_bounds__(SMALL_WAVES * 64, 1) void k_pc_small(SmallArgs a) {
+// the whole skeleton of one case in the calling workgroup: every piece of state is in LDS and every
+// output goes through the case's own pointers in `a`, so one workgroup per case may run side by side
+__device__ __forceinline__ void pc_small_body(const SmallArgs &a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int n = a.n, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     double *Cf = reinterpret_cast<double *>(smem);                                  // n x n
@@ -4604,6 +4606,16 @@ __global__ __launch_bounds__(SMALL_WAVES * 64, 1) void k_pc_small(SmallArgs a) {
         sum->status = status;
         sum->xrows = (int64_t)cnt[5];
     }
+}
+
+__global__ __launch_bounds__(SMALL_WAVES * 64, 1) void k_pc_small(SmallArgs a) { pc_small_body(a); }
+
+// one workgroup per case (pcg_skeleton_batch): the cases' arguments are an array in device memory.
+// The binomial table every case points to is built for the largest n of the batch, so rows
+// 0..n of each case's own n exist; the dynamic LDS size is the largest small_lds_bytes(n).
+__global__ __launch_bounds__(SMALL_WAVES * 64, 1) void k_pc_small_batch(const SmallArgs *cases) {
+    const SmallArgs a = cases[blockIdx.x];
+    pc_small_body(a);
 }
 
 size_t small_lds_bytes(int n) {
@@ -6111,6 +6123,23 @@ bool small_ok(const pcg_handle *h, int64_t n) {
     return h->tune[PCG_TUNE_SMALL] != 0;
 }
 
+// SmallArgs::depth_cst of one (alpha, N): make_args' per-depth constants, 4 doubles per depth
+void small_depth_cst(double alpha, int64_t N, double *cst) {
+    for (int d = 0; d <= SMALL_MAXD; ++d) {
+        const double dof = (double)N - d - 3;
+        cst[4 * d + 3] = dof < 0 ? 1.0 : 0.0;
+        cst[4 * d + 2] = dof >= 0 ? std::sqrt(dof) : 0.0;
+        if (dof > 0) {
+            const double r2 = threshold_r2(alpha, (double)N, d);
+            cst[4 * d] = r2 * (1.0 - 1e-6);
+            cst[4 * d + 1] = r2 * (1.0 + 1e-6);
+        } else {
+            cst[4 * d] = -1.0;
+            cst[4 * d + 1] = 1e300;
+        }
+    }
+}
+
 // returns PCG_OK, an error, or 1: deeper than SMALL_MAXD or a full band queue (the caller reruns
 // on the level loop)
 int skeleton_small(pcg_handle *h, const double *C, int64_t n, int64_t ldc, int64_t N, double alpha, int max_depth,
@@ -6171,19 +6200,7 @@ int skeleton_small(pcg_handle *h, const double *C, int64_t n, int64_t ldc, int64
     a.ctr = reinterpret_cast<unsigned long long *>((char *)h->small_sum.p + sizeof(SmallSummary) + 8 -
                                                    (sizeof(SmallSummary) % 8));
     double cst[4 * (SMALL_MAXD + 1)];
-    for (int d = 0; d <= SMALL_MAXD; ++d) {     // make_args' per-depth constants
-        const double dof = (double)N - d - 3;
-        cst[4 * d + 3] = dof < 0 ? 1.0 : 0.0;
-        cst[4 * d + 2] = dof >= 0 ? std::sqrt(dof) : 0.0;
-        if (dof > 0) {
-            const double r2 = threshold_r2(alpha, (double)N, d);
-            cst[4 * d] = r2 * (1.0 - 1e-6);
-            cst[4 * d + 1] = r2 * (1.0 + 1e-6);
-        } else {
-            cst[4 * d] = -1.0;
-            cst[4 * d + 1] = 1e300;
-        }
-    }
+    small_depth_cst(alpha, N, cst);
     double *cst_dev = reinterpret_cast<double *>((char *)a.ctr + 64);
     a.depth_cst = cst_dev;
     PCG_HIP(h, hipMemcpyAsync(cst_dev, cst, sizeof(cst), hipMemcpyHostToDevice, h->stream));
@@ -6280,6 +6297,222 @@ extern "C" int pcg_pc_skeleton(pcg_handle *h, const double *X, int64_t N, int64_
     const int rc = pcg_corr_launch(h, X, N, n, ldx, C, ldc);     // stream-ordered: no host sync between
     if (rc) return rc;
     return pcg_skeleton(h, C, n, ldc, N, alpha, max_depth, flags, removed_level, stats);
+}
+
+// ---------------------------------------------------------------------------------------
+// Batched small graphs: one k_pc_small_batch workgroup per case, one host wait per batch.
+// Shared by the batch: the binomial table (built for the largest n), the launch, the LDS size
+// (the largest small_lds_bytes(n)), the stream synchronise. Per case, as slices of one handle-owned
+// allocation each: the kernel arguments, K1 descriptor and depth constants (one H2D copy), the
+// summary and the near-alpha / record counters (one memset, one D2H copy), the near-alpha list.
+namespace {
+constexpr int64_t BATCH_NEAR_CAP = 1024;          // near-alpha records kept per case
+constexpr size_t BATCH_CST = 4 * (SMALL_MAXD + 1);
+constexpr size_t BATCH_SUM_STRIDE = (sizeof(SmallSummary) + 63) / 64 * 64;
+
+// the handle after a batch (or before its kernels): no run's rows, degrees or records are held
+void batch_reset_run_state(pcg_handle *h) {
+    h->C = nullptr;
+    h->rl = nullptr;
+    h->n = 0;
+    h->W = 1;
+    h->depth = -1;
+    h->deg_levels.clear();
+    h->xpending[0] = h->xpending[1] = false;
+    h->xany = false;
+    h->xinl = false;
+    h->export_rows = 0;
+    h->need_cap = 0;
+    export_to_own(h, h->export_cap);
+    h->rec_h.clear(); h->near_h.clear();
+    h->rec_total = h->near_total = 0;
+    h->near_seen = h->near_total_dev = 0;
+    memset(&h->st, 0, sizeof(h->st));
+}
+}  // namespace
+
+extern "C" int pcg_skeleton_batch(pcg_handle *h, const pcg_case *cases, int64_t count, double alpha, int max_depth,
+                                  int flags, pcg_case_result *results) {
+    if (!h) return PCG_ERR_INVALID;
+    if (count < 0 || count > (1 << 20) || (count > 0 && (!cases || !results)) || !(alpha > 0 && alpha < 1))
+        return pcg_fail(h, PCG_ERR_INVALID, "pcg_skeleton_batch: invalid arguments (count=%lld)", (long long)count);
+    if (flags & ~(PCG_FLAG_FULL_P | PCG_FLAG_EXACT_ALL))
+        return pcg_fail(h, PCG_ERR_INVALID, "pcg_skeleton_batch: flags 0x%x (only FULL_P and EXACT_ALL run in a batch)",
+                        flags);
+    if (h->banned || h->world != 1 || h->rm_ext)
+        return pcg_fail(h, PCG_ERR_INVALID, "pcg_skeleton_batch: forbidden pairs, a world size != 1 and a caller-owned "
+                                            "removal buffer are not supported in a batch");
+    int nmax = 0;
+    bool any_x = false;
+    for (int64_t i = 0; i < count; ++i) {
+        const pcg_case &cs = cases[i];
+        if (cs.n < 2 || cs.n > SMALL_N || !cs.C || cs.ldc < cs.n || !cs.removed_level || !cs.sep_xy || !cs.sep_bits ||
+            (cs.X && (cs.N < 2 || cs.ldx < cs.n)))
+            return pcg_fail(h, PCG_ERR_INVALID, "pcg_skeleton_batch: case %lld invalid (n=%lld, 2..%d)", (long long)i,
+                            (long long)cs.n, SMALL_N);
+        nmax = std::max(nmax, (int)cs.n);
+        any_x = any_x || cs.X != nullptr;
+    }
+    h->batch_near_h.assign((size_t)count, {});
+    if (count == 0) return PCG_OK;
+    PCG_HIP(h, hipSetDevice(h->device));
+    if (h->xs) PCG_HIP(h, hipStreamSynchronize(h->xs));
+    batch_reset_run_state(h);
+    const size_t B = (size_t)count;
+    const size_t args_bytes = (sizeof(SmallArgs) * B + 63) / 64 * 64;
+    const size_t corr_bytes = (sizeof(CorrSmallCase) * B + 63) / 64 * 64;
+    const size_t up_bytes = args_bytes + corr_bytes + sizeof(double) * BATCH_CST * B;
+    const size_t sum_bytes = BATCH_SUM_STRIDE * B, ctr_bytes = 2 * sizeof(unsigned long long) * B;
+    const int64_t near_cap = std::min<int64_t>(std::max<int64_t>(h->near_cap, 1), BATCH_NEAR_CAP);
+    if (!pcg_ensure(h, h->batch_up, up_bytes) || !pcg_ensure_pinned(h, h->batch_up_pin, up_bytes) ||
+        !pcg_ensure(h, h->batch_sum, sum_bytes + ctr_bytes) ||
+        !pcg_ensure_pinned(h, h->batch_sum_pin, sum_bytes + ctr_bytes) ||
+        !pcg_ensure(h, h->batch_near, sizeof(pcg_record) * (size_t)near_cap * B) ||
+        !pcg_ensure(h, h->records, sizeof(pcg_record) * std::max<int64_t>(h->rec_cap, 1)))
+        return pcg_fail(h, PCG_ERR_OOM, "pcg_skeleton_batch buffers (%lld cases)", (long long)count);
+    // one table for the batch, built for its largest n: every case reads rows <= its own n of it.
+    // binom_n names the table that is on the device, so a following run of another n rebuilds it
+    if (h->binom_n != nmax) {
+        build_binom(h, nmax);
+        if (!pcg_ensure(h, h->binom, sizeof(uint64_t) * h->binom_h.size())) return PCG_ERR_OOM;
+        PCG_HIP(h, hipMemcpyAsync(h->binom.p, h->binom_h.data(), sizeof(uint64_t) * h->binom_h.size(),
+                                  hipMemcpyHostToDevice, h->stream));
+        h->binom_n = nmax;
+    }
+    SmallArgs *args = (SmallArgs *)h->batch_up_pin.p;
+    CorrSmallCase *cc = (CorrSmallCase *)((char *)h->batch_up_pin.p + args_bytes);
+    double *cst = (double *)((char *)h->batch_up_pin.p + args_bytes + corr_bytes);
+    char *up_dev = (char *)h->batch_up.p;
+    char *sum_dev = (char *)h->batch_sum.p;
+    const int qcap = (int)std::min<int64_t>(std::max<int64_t>(h->tune[PCG_TUNE_SMALL_QCAP], 1), SMALL_QCAP);
+    size_t lds = 0;
+    int64_t cst_N = 0;
+    const double *cst_of_N = nullptr;      // the last case's constants serve the next case of the same N
+    for (size_t i = 0; i < B; ++i) {
+        const pcg_case &cs = cases[i];
+        SmallArgs a{};
+        a.C = cs.C; a.ldc = cs.ldc; a.n = (int)cs.n; a.max_depth = max_depth; a.alpha = alpha; a.tau = PCG_COND_TAU;
+        a.banned = nullptr;
+        a.binom = (const uint64_t *)h->binom.p;
+        a.rl = cs.removed_level;
+        a.xy = cs.sep_xy;
+        a.bits = cs.sep_bits;
+        a.nearl = (pcg_record *)h->batch_near.p + (size_t)near_cap * i;
+        a.records = (pcg_record *)h->records.p;
+        a.near_cap = near_cap;
+        a.rec_cap = 0;
+        a.fullp = (flags & PCG_FLAG_FULL_P) ? 1 : 0;
+        a.record = 0;
+        a.exact_all = (flags & PCG_FLAG_EXACT_ALL) ? 1 : 0;
+        a.qcap = qcap;
+        a.sum = (SmallSummary *)(sum_dev + BATCH_SUM_STRIDE * i);
+        a.ctr = (unsigned long long *)(sum_dev + sum_bytes) + 2 * i;
+        a.depth_cst = (const double *)(up_dev + args_bytes + corr_bytes) + BATCH_CST * i;
+        args[i] = a;
+        CorrSmallCase k{};
+        k.X = cs.X; k.C = cs.C; k.N = cs.N; k.ldx = cs.ldx; k.ldc = cs.ldc; k.n = (int32_t)cs.n;
+        cc[i] = k;
+        if (cst_of_N && cst_N == cs.N) memcpy(cst + BATCH_CST * i, cst_of_N, sizeof(double) * BATCH_CST);
+        else small_depth_cst(alpha, cs.N, cst + BATCH_CST * i);
+        cst_of_N = cst + BATCH_CST * i;
+        cst_N = cs.N;
+        lds = std::max(lds, small_lds_bytes((int)cs.n));
+    }
+    PCG_HIP(h, hipMemcpyAsync(h->batch_up.p, h->batch_up_pin.p, up_bytes, hipMemcpyHostToDevice, h->stream));
+    if (any_x) {
+        const int rc = corr_small_batch_launch(h, (const CorrSmallCase *)(up_dev + args_bytes), count);
+        if (rc) return rc;
+    }
+    PCG_HIP(h, hipMemsetAsync(sum_dev + sum_bytes, 0, ctr_bytes, h->stream));
+    hipLaunchKernelGGL(k_pc_small_batch, dim3((unsigned)B), dim3(SMALL_WAVES * 64), lds, h->stream,
+                       (const SmallArgs *)h->batch_up.p);
+    PCG_HIP(h, hipGetLastError());
+    PCG_HIP(h, hipMemcpyAsync(h->batch_sum_pin.p, h->batch_sum.p, sum_bytes + ctr_bytes, hipMemcpyDeviceToHost,
+                              h->stream));
+    PCG_HIP(h, hipStreamSynchronize(h->stream));
+    int wall_khz = 100000;            // wall_clock64's rate (kHz)
+    (void)hipDeviceGetAttribute(&wall_khz, hipDeviceAttributeWallClockRate, h->device);
+    if (wall_khz <= 0) wall_khz = 100000;
+    const unsigned long long *ctrs = (const unsigned long long *)((const char *)h->batch_sum_pin.p + sum_bytes);
+    std::vector<size_t> rerun;
+    for (size_t i = 0; i < B; ++i) {
+        const SmallSummary *sm = (const SmallSummary *)((const char *)h->batch_sum_pin.p + BATCH_SUM_STRIDE * i);
+        pcg_case_result &r = results[i];
+        memset(&r, 0, sizeof(r));
+        if (sm->status & 12) {          // deeper than SMALL_MAXD or a full band queue: the level loop, below
+            rerun.push_back(i);
+            continue;
+        }
+        const int n = (int)cases[i].n, L = sm->levels;
+        r.stats.levels = L;
+        r.stats.driver = PCG_DRIVER_SMALL;
+        for (int d = 0; d < L; ++d) {
+            r.stats.tests[d] = sm->tests[d];
+            r.stats.calls[d] = sm->calls[d];
+            r.stats.indep[d] = sm->indep[d];
+            r.stats.exact[d] = sm->exact[d];
+            r.stats.near_alpha[d] = sm->near_alpha[d];
+            r.stats.edges_after[d] = sm->edges_after[d];
+            r.stats.max_degree[d] = sm->max_degree[d];
+            r.stats.level_ms[d] = r.stats.kernel_ms[d] = (double)(sm->stamp[d + 1] - sm->stamp[d]) / wall_khz;
+            memcpy(r.deg[d], sm->deg[d], sizeof(int32_t) * n);
+        }
+        r.sep_rows = sm->xrows;
+        const int64_t nn = std::min<int64_t>((int64_t)ctrs[2 * i], near_cap);
+        if (nn > 0) {
+            h->batch_near_h[i].resize((size_t)nn);
+            PCG_HIP(h, hipMemcpy(h->batch_near_h[i].data(), (pcg_record *)h->batch_near.p + (size_t)near_cap * i,
+                                 sizeof(pcg_record) * nn, hipMemcpyDeviceToHost));
+        }
+        r.near_alpha_count = nn;
+        if (sm->status & 3) r.rc = r.stats.error = (sm->status & 1) ? PCG_ERR_SINGULAR : PCG_ERR_DOMAIN;
+    }
+    // the cases the small kernel gave up on, one by one on the level loop as pcg_skeleton reruns
+    // them; their rows are copied into the case's own buffers before the next one starts
+    for (size_t i : rerun) {
+        const pcg_case &cs = cases[i];
+        pcg_case_result &r = results[i];
+        int rc = PCG_OK;
+        for (int attempt = 0; attempt < 6; ++attempt) {
+            rc = skeleton_once(h, cs.C, cs.n, cs.ldc, cs.N, alpha, max_depth, flags, cs.removed_level);
+            if (rc != PCG_ERR_OVERFLOW) break;
+        }
+        if (rc == PCG_ERR_HIP || rc == PCG_ERR_OOM || rc == PCG_ERR_INVALID) return rc;
+        h->st.driver = PCG_DRIVER_SMALL_RERUN;
+        r.stats = h->st;
+        r.rc = rc;
+        if (rc == PCG_OK) {
+            rc = export_sync(h);
+            if (rc) return rc;
+            const int64_t rows = h->export_rows;
+            if (rows > cs.n * (cs.n - 1))
+                return pcg_fail(h, PCG_ERR_OVERFLOW, "pcg_skeleton_batch: case %zu exported %lld rows", i, (long long)rows);
+            if (rows > 0) {
+                PCG_HIP(h, hipMemcpyAsync(cs.sep_xy, h->dst_xy, sizeof(int32_t) * 2 * rows, hipMemcpyDeviceToDevice,
+                                          h->stream));
+                PCG_HIP(h, hipMemcpyAsync(cs.sep_bits, h->dst_bits, sizeof(uint64_t) * rows, hipMemcpyDeviceToDevice,
+                                          h->stream));
+            }
+            r.sep_rows = rows;
+            const int L = std::min<int>(h->st.levels, PCG_MAX_LEVELS);
+            for (int d = 0; d < L && (size_t)(d + 1) * cs.n <= h->deg_levels.size(); ++d)
+                memcpy(r.deg[d], h->deg_levels.data() + (size_t)d * cs.n, sizeof(int32_t) * cs.n);
+            h->batch_near_h[i] = h->near_h;
+            r.near_alpha_count = (int64_t)h->near_h.size();
+        }
+        PCG_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    if (!rerun.empty()) batch_reset_run_state(h);
+    return PCG_OK;
+}
+
+extern "C" int pcg_batch_near_export(pcg_handle *h, int64_t case_index, pcg_record *rec_host, int64_t count) {
+    if (!h || case_index < 0 || case_index >= (int64_t)h->batch_near_h.size() || count < 0 ||
+        count > (int64_t)h->batch_near_h[(size_t)case_index].size() || (count > 0 && !rec_host))
+        return pcg_fail(h, PCG_ERR_INVALID, "pcg_batch_near_export: case %lld, count %lld", (long long)case_index,
+                        (long long)count);
+    if (count) memcpy(rec_host, h->batch_near_h[(size_t)case_index].data(), sizeof(pcg_record) * count);
+    return PCG_OK;
 }
 
 // wait for the queued sepset exports and take their row count (the export stream's counter)

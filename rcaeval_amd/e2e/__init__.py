@@ -46,8 +46,9 @@ def _dummy(args, kwargs):
 
 from .circa import circa  # noqa: E402
 from .cloudranger import cloudranger  # noqa: E402
-from .pc_pagerank import pc_pagerank  # noqa: E402
+from .pc_pagerank import pc_pagerank, pc_pagerank_batch  # noqa: E402
 from .fci_pagerank import fci_pagerank  # noqa: E402
 from .pc_randomwalk import fci_randomwalk, pc_randomwalk  # noqa: E402
 
-__all__ = ["rca", "circa", "cloudranger", "fci_pagerank", "fci_randomwalk", "pc_pagerank", "pc_randomwalk"]
+__all__ = ["rca", "circa", "cloudranger", "fci_pagerank", "fci_randomwalk", "pc_pagerank", "pc_pagerank_batch",
+           "pc_randomwalk"]

@@ -43,3 +43,41 @@ def pc_pagerank(data, inject_time=None, dataset=None, dk_select_useful=False, wi
     with phase("rank sort"):
         ranked = sorted(zip(node_names, scores), key=lambda t: t[1], reverse=True)
     return {"adj": M, "node_names": node_names, "ranks": [name for name, _ in ranked]}
+
+
+def pc_pagerank_batch(cases, dataset=None, dk_select_useful=False, **kwargs) -> list:
+    """``[pc_pagerank(data, inject_time, dataset=dataset) for (data, inject_time) in cases]`` with
+    the PC runs of all cases batched (``causal.pc_batch``: one K1 launch, one skeleton launch, one
+    host wait). ``cases``: data frames, or (data, inject_time) pairs. Preprocessing, the digraph,
+    PageRank and the rank sort stay per case, as in ``pc_pagerank``. A case whose preprocessing
+    or PC raises goes through ``pc_pagerank`` itself, i.e. the ``@rca`` wrapper's route (dummy
+    ranks for data errors, engine faults propagate)."""
+    from ..causal import pc_batch
+    items = [c if isinstance(c, (tuple, list)) else (c, None) for c in cases]
+    out: list = [None] * len(items)
+    pre = []
+    for i, (data, _inject) in enumerate(items):
+        try:
+            with phase("preprocess"):
+                d = preprocess(data=data, dataset=dataset, dk_select_useful=dk_select_useful)
+                pre.append((i, d.columns.to_list(), d.to_numpy()))
+        except Exception:      # noqa: BLE001 - pc_pagerank below repeats it under @rca
+            pass
+    cgs = pc_batch([X for _, _, X in pre], return_exceptions=True) if pre else []
+    for (i, node_names, _X), cg in zip(pre, cgs):
+        if isinstance(cg, Exception):
+            continue
+        try:
+            with phase("digraph"):
+                M, _nodes = digraph_matrix(cg.G.graph)
+            with phase("pagerank"):
+                scores = PageRank().fit_transform(M.T)
+            with phase("rank sort"):
+                ranked = sorted(zip(node_names, scores), key=lambda t: t[1], reverse=True)
+            out[i] = {"adj": M, "node_names": node_names, "ranks": [name for name, _ in ranked]}
+        except Exception:      # noqa: BLE001
+            out[i] = None
+    for i, (data, inject) in enumerate(items):
+        if out[i] is None:
+            out[i] = pc_pagerank(data, inject, dataset=dataset, dk_select_useful=dk_select_useful, **kwargs)
+    return out

@@ -35,6 +35,8 @@ class SkeletonOut:
     ``sep_bits``) are copied to the host on first access.
     """
 
+    rc = 0      # PCG_OK, or a batch case's own error code (Engine.skeleton_batch raises nothing per case)
+
     def __init__(self, n, rl_dev, xy_dev, bits_dev, deg_levels, stats, records=None, near_alpha=None,
                  device_ms=0.0):
         self.n = n
@@ -350,6 +352,96 @@ class Engine:
         out.extra["collect_ms"] = 1000.0 * (time.perf_counter() - t0)
         out.extra["device_ms"] = out.device_ms
         return out, C
+
+    def skeleton_batch(self, Cs_or_Xs, Ns=None, alpha: float = 0.05, max_depth: int = -1, flags: int = 0,
+                       from_data: bool = False) -> list:
+        """Many small cases (2 <= n <= 64) in one launch and one host wait (``pcg_skeleton_batch``).
+
+        ``Cs_or_Xs``: one n x n correlation matrix per case with its sample count in ``Ns``, or —
+        ``from_data=True`` — one N x n data array per case (``Ns`` is then taken from the arrays;
+        the batched K1 computes each C, kept as ``out.extra["C"]``). The cases are packed into one
+        device allocation each for X / C, removal depths, sepset (x, y) and sepset words; every
+        result holds views of its own slice, already copied to the host in one transfer each.
+        A case that failed (singular / math domain) raises nothing: its ``SkeletonOut.rc`` and
+        ``stats["error"]`` carry the code. ``flags``: PCG_FLAG_FULL_P and PCG_FLAG_EXACT_ALL."""
+        torch = _torch()
+        arrs = [a if isinstance(a, torch.Tensor) else np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+                for a in Cs_or_Xs]
+        B = len(arrs)
+        if B == 0:
+            return []
+        for a in arrs:
+            if a.ndim != 2 or (not from_data and a.shape[0] != a.shape[1]):
+                raise ValueError(f"skeleton_batch: case of shape {tuple(a.shape)}")
+        ns = [int(a.shape[1]) for a in arrs]
+        if from_data:
+            Nl = [int(a.shape[0]) for a in arrs]
+        else:
+            if Ns is None:
+                raise ValueError("skeleton_batch: Ns (one sample count per case) is required for correlation input")
+            Nl = [int(Ns)] * B if np.isscalar(Ns) else [int(v) for v in Ns]
+            if len(Nl) != B:
+                raise ValueError("skeleton_batch: one N per case")
+        # one packed device buffer per kind
+        if all(isinstance(a, np.ndarray) for a in arrs):
+            # packed in a page-locked staging buffer kept by the engine (grow-only), one H2D copy;
+            # the copy is blocking, so the buffer is free again when the next batch packs into it
+            total = sum(a.size for a in arrs)
+            pin = getattr(self, "_batch_pin", None)
+            if pin is None or pin.numel() < total:
+                pin = self._batch_pin = torch.empty(total + total // 4, dtype=torch.float64, pin_memory=True)
+            stage, o = pin.numpy(), 0
+            for a in arrs:
+                stage[o:o + a.size] = a.reshape(-1)
+                o += a.size
+            flat = torch.empty(total, dtype=torch.float64, device=self.device)
+            flat.copy_(pin[:total])
+        else:
+            flat = torch.cat([self.to_device(a).reshape(-1) for a in arrs])
+        sq = np.array([n * n for n in ns], np.int64)
+        rows_cap = np.array([max(n * (n - 1), 1) for n in ns], np.int64)
+        in_off = np.concatenate([[0], np.cumsum([a.shape[0] * a.shape[1] for a in arrs])])
+        sq_off = np.concatenate([[0], np.cumsum(sq)])
+        row_off = np.concatenate([[0], np.cumsum(rows_cap)])
+        Call = torch.empty(int(sq_off[-1]), dtype=torch.float64, device=self.device) if from_data else flat
+        rl = torch.empty(int(sq_off[-1]), dtype=torch.int8, device=self.device)
+        xy = torch.empty((int(row_off[-1]), 2), dtype=torch.int32, device=self.device)
+        bits = torch.empty((int(row_off[-1]), 1), dtype=torch.int64, device=self.device)
+        cases = (_lib.PcgCase * B)()
+        pin, pC, prl, pxy, pbits = flat.data_ptr(), Call.data_ptr(), rl.data_ptr(), xy.data_ptr(), bits.data_ptr()
+        for i in range(B):
+            c = cases[i]
+            c.X = pin + 8 * int(in_off[i]) if from_data else None
+            c.N, c.n, c.ldx = Nl[i], ns[i], ns[i]
+            c.C = pC + 8 * int(sq_off[i])
+            c.ldc = ns[i]
+            c.removed_level = prl + int(sq_off[i])
+            c.sep_xy = pxy + 8 * int(row_off[i])
+            c.sep_bits = pbits + 8 * int(row_off[i])
+        res = (_lib.PcgCaseResult * B)()
+        check(self.h, self.lib.pcg_skeleton_batch(self.h, cases, B, float(alpha), int(max_depth), int(flags), res),
+              "pcg_skeleton_batch")
+        # the call returned after the handle's stream was synchronised: every result is complete
+        rl_h, xy_h, bits_h = rl.cpu().numpy(), xy.cpu().numpy(), bits.cpu().numpy()
+        outs = []
+        for i in range(B):
+            r, n = res[i], ns[i]
+            rows = int(r.sep_rows)
+            s0, r0 = int(sq_off[i]), int(row_off[i])
+            L = int(r.stats.levels)
+            deg = np.ctypeslib.as_array(r.deg)[:L, :n].copy()
+            near = np.zeros(int(r.near_alpha_count), RECORD_DTYPE)
+            if len(near):
+                check(self.h, self.lib.pcg_batch_near_export(self.h, i, near.ctypes.data_as(ctypes.c_void_p), len(near)),
+                      "pcg_batch_near_export")
+            out = SkeletonOut(n, rl[s0:s0 + n * n].view(n, n), xy[r0:r0 + rows], bits[r0:r0 + rows], deg,
+                              r.stats.as_dict(), np.zeros(0, RECORD_DTYPE), near)
+            out.rc = int(r.rc)
+            out._host = {"rl": rl_h[s0:s0 + n * n].reshape(n, n), "xy": xy_h[r0:r0 + rows],
+                         "bits": bits_h[r0:r0 + rows]}
+            out.extra["C"] = Call[s0:s0 + n * n].view(n, n)
+            outs.append(out)
+        return outs
 
     def _collect(self, n: int, rl, st: PcgStats, events=None) -> SkeletonOut:
         # the sepset rows' device copies are enqueued first (they are the step's last device work);

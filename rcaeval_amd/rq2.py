@@ -282,15 +282,82 @@ def stop_loaders() -> None:
         _LOADERS = None
 
 
+def process_loaded_batch(cs: list, dataset: str, result_path: str) -> list:
+    """``process_loaded`` of several loaded cases with their PC runs batched
+    (``e2e.pc_pagerank_batch``); the JSON files are written in the order of ``cs``. If the batch
+    itself raises (an engine fault), the cases run one by one instead, so the files of the cases
+    before the failing one are written and the error is raised at that case's position."""
+    from .e2e import pc_pagerank_batch
+    t0 = time.perf_counter()
+    try:
+        outs = pc_pagerank_batch([(c["data"], c["inject_time"]) for c in cs], dataset=dataset,
+                                 dk_select_useful=False)
+    except Exception:      # noqa: BLE001 - repeated per case below, raised where it belongs
+        return [process_loaded(c, "pc_pagerank", dataset, result_path) for c in cs]
+    seconds = (time.perf_counter() - t0) / max(len(cs), 1)
+    res = []
+    for c, out in zip(cs, outs):
+        for k, v in c.get("load_s", {}).items():
+            phases.add(k, v)
+        phases.add("method (total)", seconds)
+        ranks = out.get("ranks")
+        rp = join(result_path, c["result_name"])
+        with phases.phase("json"):
+            dump_json(filename=rp, data={0: ranks})
+        res.append({"path": rp, "ranks": ranks, "seconds": seconds})
+    return res
+
+
+def _run_batched(mine: list, dataset: str, result_path: str, batch: int, prefetch: int, loader: str,
+                 kw: dict) -> list:
+    """``run``'s case loop for ``batch > 0``: groups of up to ``batch`` consecutive cases of the
+    sorted list, the next group loading while the current one runs. A case whose load fails
+    raises after the cases before it were processed, as in the sequential loop."""
+    from concurrent.futures import ThreadPoolExecutor
+    groups = [mine[i:i + batch] for i in range(0, len(mine), batch)]
+    own = None
+    if loader == "process" and prefetch > 0:
+        ex = start_loaders(prefetch)
+    else:
+        ex = own = ThreadPoolExecutor(max_workers=max(prefetch, 1))
+    per_case = []
+    pending: list = []
+    try:
+        pending = [ex.submit(load_case, p, **kw) for p in groups[0]] if groups else []
+        for g in range(len(groups)):
+            futs = pending
+            pending = [ex.submit(load_case, p, **kw) for p in groups[g + 1]] if g + 1 < len(groups) else []
+            loaded, err = [], None
+            for f in futs:
+                try:
+                    loaded.append(f.result())
+                except Exception as e:      # noqa: BLE001 - raised below, after the cases before it
+                    err = e
+                    break
+            if loaded:
+                per_case.extend(process_loaded_batch(loaded, dataset, result_path))
+            if err is not None:
+                raise err
+    finally:
+        for f in pending:
+            f.cancel()
+        if own is not None:
+            own.shutdown(wait=True)
+    return per_case
+
+
 def run(dataset_dir: str, method: str, dataset: str, output: str = "output", length=None, tdelta: int = 0,
-        test: bool = False, rank: int = 0, world: int = 1, prefetch: int = 2, loader: str = "thread") -> dict:
+        test: bool = False, rank: int = 0, world: int = 1, prefetch: int = 2, loader: str = "thread",
+        batch: int = 0) -> dict:
     """Every case of ``dataset_dir`` through ``method``; rank ``r`` of ``world`` takes cases
     ``r, r + world, ...`` of the sorted list. Returns this rank's timings and, on rank 0,
     the evaluation (after a barrier when ``world > 1``). ``prefetch`` loaders read the next
     cases ahead of the GPU thread: threads by default (safe from any caller); ``loader="process"``
     uses spawned processes (faster — pandas' parser holds the GIL — but the caller's script needs
     an ``if __name__ == "__main__"`` guard; ``main`` and ``bench.py`` opt in, and ``main`` stops them
-    at its end)."""
+    at its end). ``batch=B`` (> 0, method ``pc_pagerank`` only; 0 = the per-case loop) runs the PC of
+    up to B consecutive cases in one batched launch (``e2e.pc_pagerank_batch``); the result files
+    are still written in sorted case order."""
     is_synthetic = "circa" in dataset or "rcd" in dataset
     result_path = join(output, "results")
     os.makedirs(result_path, exist_ok=True)
@@ -298,7 +365,10 @@ def run(dataset_dir: str, method: str, dataset: str, output: str = "output", len
     mine = paths[rank::world]
     t0 = time.perf_counter()
     per_case = []
-    if prefetch > 0 and len(mine) > 1:
+    if batch > 0 and method == "pc_pagerank":
+        per_case = _run_batched(mine, dataset, result_path, int(batch), prefetch, loader,
+                                dict(length=length, tdelta=tdelta, is_synthetic=is_synthetic))
+    elif prefetch > 0 and len(mine) > 1:
         # loaders (threads by default, or spawned processes) read and window the next cases while this
         # thread runs the current case on the GPU; cases are still processed, and their errors
         # raised, in the sorted order of the sequential loop
@@ -354,6 +424,8 @@ def main(argv=None):
     ap.add_argument("--length", type=int, default=None)
     ap.add_argument("--tdelta", type=int, default=0)
     ap.add_argument("--test", action="store_true")
+    ap.add_argument("--batch", type=int, default=0,
+                    help="pc_pagerank: run the PC of up to this many cases in one batched launch (0 = per case)")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -367,7 +439,7 @@ def main(argv=None):
         raise SystemExit(f"{dataset_dir} not found (datasets are not downloaded here)")
     try:
         res = run(dataset_dir, args.method, args.dataset, args.output, args.length, args.tdelta, args.test,
-                  rank, world, loader="process")
+                  rank, world, loader="process", batch=args.batch)
     finally:
         stop_loaders()
     if rank == 0:

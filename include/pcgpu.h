@@ -477,6 +477,32 @@ int pcg_chisq_batch(pcg_handle *h, const int32_t *data, int64_t N, int64_t n, co
                     const int32_t *tests, int32_t stride, int64_t count, int g_sq, int64_t max_cells,
                     double *stat, int64_t *df, int32_t *status);
 
+/* ---- pairwise Granger regressions (granger_pagerank / granger_randomwalk) ------------
+ * Replaces the n*(n-1) statsmodels `grangercausalitytests` calls [U] (statsmodels 0.14.0) of
+ * RCAEval/graph_construction/granger.py:13-34. X: device T x n doubles, row stride ldx (rows are
+ * time), 2 <= n <= 4096 (the five outputs are n * n * maxlag * 32 bytes: 1.6 GB at the limit; the
+ * handle adds T * n doubles and n * n * maxlag int32 of scratch). maxlag in 1..3 (anything else:
+ * PCG_ERR_INVALID); T <= 3 * maxlag + 1 is refused with
+ * PCG_ERR_DOMAIN ("Insufficient observations") before anything is read. Per item
+ * (i, j, L) = caused column i, causing column j, lag L, at index (i * n + j) * maxlag + L - 1,
+ * over the window t = L..T-1: ssr_r of y_t ~ [y_{t-1..t-L}, 1], ssr_u of
+ * y_t ~ [y_{t-1..t-L}, x_{t-1..t-L}, 1] (least-squares SSR also of a rank-deficient design, as
+ * by pseudo-inverse), tss the centred sum of squares of y_t, rank of the joint design
+ * (df_resid = T - L - rank). ssr_r, ssr_u, tss: device n*n*maxlag doubles out; rank, status:
+ * device n*n*maxlag int32 out. status: 0 ok, 1 a lagged column is constant over its window,
+ * 2 perfect fit (tss == 0, ssr_u == 0 or ssr_u / tss < 2^-52), 3 ok, computed by the exact
+ * (Householder QR) path (informational), 4 non-finite input; ssr is NaN and rank 0 under 1, 2
+ * (from a constant y window) and 4, and on the diagonal (status 0). exact_items: host out, the
+ * items the exact path computed (may be NULL). The caller takes the F / chi-square tails (the
+ * tests of `grangercausalitytests`) and raises on status 1, 2, 4. Synchronous on return.       */
+int pcg_granger(pcg_handle *h, const double *X, int64_t T, int64_t n, int64_t ldx, int maxlag,
+                double *ssr_r, double *ssr_u, double *tss, int32_t *rank, int32_t *status,
+                int64_t *exact_items);
+/* The guards pcg_granger's moment / Cholesky path was built with (host-only, any may be NULL): an
+ * item keeps that path's result only if every scaled pivot >= tau, ssr_u / tss >= floor and
+ * (1 + |beta|_1)^2 <= beta_c / tau; the documented error bound is a function of the three.      */
+int pcg_granger_guards(double *tau, double *floor, double *beta_c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,8 @@ SIGNATURES = [
     ("pcg_set_forbidden_pairs", I32, [P, P]),
     ("pcg_fisherz_batch", I32, [P, P, I64, I64, I64, P, I32, I64, P, P]),
     ("pcg_chisq_batch", I32, [P, P, I64, I64, P, P, I32, I64, ctypes.c_int, I64, P, P, P]),
+    ("pcg_granger", I32, [P, P, I64, I64, I64, ctypes.c_int, P, P, P, P, P, ctypes.POINTER(I64)]),
+    ("pcg_granger_guards", I32, [ctypes.POINTER(D), ctypes.POINTER(D), ctypes.POINTER(D)]),
 ]
 
 _lib = None

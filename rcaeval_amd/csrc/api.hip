@@ -173,7 +173,8 @@ extern "C" int pcg_destroy(pcg_handle *h) {
                       &h->ug2[1], &h->exp_ctr, &h->cpre, &h->binom, &h->ctr,
                       &h->deferred, &h->screenq, &h->records, &h->nearbuf, &h->exportbuf, &h->export_xy, &h->diag,
                       &h->colmean, &h->pr_scratch, &h->batch_scratch, &h->chisq_scratch, &h->cblk, &h->lmk,
-                      &h->k1_digits, &h->small_sum, &h->batch_up, &h->batch_sum, &h->batch_near};
+                      &h->k1_digits, &h->small_sum, &h->batch_up, &h->batch_sum, &h->batch_near,
+                      &h->granger_scratch, &h->granger_work};
     for (DevBuf *b : bufs)
         if (b->p) hipFree(b->p);
     PinBuf *pins[] = {&h->ctr_pin, &h->deg_pin, &h->off_pin, &h->cpre_pin, &h->status_pin, &h->small_pin,

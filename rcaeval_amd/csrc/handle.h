@@ -77,6 +77,7 @@ struct pcg_handle {
     DevBuf screenq;                 // fp32 sweep -> fp64 screen list (k_level_lds_f -> k_screen)
     DevBuf adj, deg, rm, cpre, binom, ctr, deferred, records, nearbuf, exportbuf, export_xy, diag, colmean,
         pr_scratch, batch_scratch, chisq_scratch;
+    DevBuf granger_scratch, granger_work;   // pcg_granger: Z / statistics / exact list; the exact path's designs
     DevBuf k1_digits;               // K1 int8 digit / residue planes of the centred X (corr.hip)
     // the (N, n, k, b) a CRT-mode pcg_corr_shard computed h->colmean's column exponents for;
     // pcg_corr_shard_finish refuses to rebuild C from exponents of any other call

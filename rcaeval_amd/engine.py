@@ -521,6 +521,25 @@ class Engine:
                                                ctypes.c_void_p(st.data_ptr())), "pcg_chisq_batch")
         return stat.cpu().numpy(), df.cpu().numpy(), st.cpu().numpy()
 
+    def granger(self, X, maxlag: int = 3) -> dict:
+        """Pairwise Granger regressions of a T x n array (``pcg_granger``): host arrays ``ssr_r``,
+        ``ssr_u``, ``tss`` (float64), ``rank``, ``status`` (int32), each n x n x maxlag with item
+        [i, j, L - 1] = column j causing column i at lag L, and ``exact_items``, the number of
+        items the exact path computed. ``T <= 3 * maxlag + 1`` raises ``ValueError``."""
+        torch = _torch()
+        Xd = self.to_device(X)
+        T, n = Xd.shape
+        shape = (n, n, int(maxlag))
+        f = [torch.empty(shape, dtype=torch.float64, device=self.device) for _ in range(3)]
+        k = [torch.empty(shape, dtype=torch.int32, device=self.device) for _ in range(2)]
+        exact = ctypes.c_int64()
+        check(self.h, self.lib.pcg_granger(self.h, ctypes.c_void_p(Xd.data_ptr()), int(T), int(n), int(n), int(maxlag),
+                                           *(ctypes.c_void_p(t.data_ptr()) for t in f + k), ctypes.byref(exact)),
+              "pcg_granger")
+        out = {name: t.cpu().numpy() for name, t in zip(("ssr_r", "ssr_u", "tss", "rank", "status"), f + k)}
+        out["exact_items"] = int(exact.value)
+        return out
+
     # ------------------------------------------------------------------ K4
     def pagerank_dense(self, A, damping: float = 0.85, n_iter: int = 10, tol: float = 1e-6) -> np.ndarray:
         torch = _torch()

@@ -503,6 +503,32 @@ int pcg_granger(pcg_handle *h, const double *X, int64_t T, int64_t n, int64_t ld
  * (1 + |beta|_1)^2 <= beta_c / tau; the documented error bound is a function of the three.      */
 int pcg_granger_guards(double *tau, double *floor, double *beta_c);
 
+/* ---- DirectLiNGAM causal order (micro_diag) -------------------------------------------
+ * Replaces the order search of causal-learn's `DirectLiNGAM().fit(X)` [U] (0.1.3.3, measure
+ * 'pwling', no prior knowledge) behind RCAEval/e2e/lingam_pagerank.py:52-81. X: device T x n
+ * doubles, row stride ldx (rows are samples). 1 <= n <= 4096 and T >= 2, anything else is
+ * PCG_ERR_DOMAIN. The handle keeps two T x n doubles and one n x n of scratch. Both calls are
+ * synchronous on return. Non-finite values are not refused: NaN flows as in numpy (a constant
+ * column standardizes to NaN, and np.argmax takes the first NaN).
+ *
+ * pcg_lingam_pair_scores: one search step over all m columns of X. With z the columns
+ * standardized (ddof 0), residual(a, b) = a - (cov_ddof1(a, b) / var_ddof0(b)) * b,
+ * ri = residual(zi, zj), rj = residual(zj, zi) and
+ * H(u) = (1 + log(2 pi)) / 2 - 79.047 (mean(log cosh u) - 0.37457)^2 - 7.4129 mean(u exp(-u^2/2))^2:
+ * D[i * m + j] = (H(zj) + H(ri / std(ri))) - (H(zi) + H(rj / std(rj))), D[j * m + i] = -D[i * m + j]
+ * exactly, zero diagonal; M[i] = -sum_{j != i} min(0, D_ij)^2 with a NaN-propagating min.
+ * D: device m * m doubles out; M: device m doubles out, may be NULL.
+ *
+ * pcg_direct_lingam_order: the full loop. n times: score the remaining columns U as above,
+ * m = U[np.argmax(M)] (the first NaN if any, else the first maximum; a lone remaining column is
+ * taken unscored), X_[:, i] -= (cov_ddof1 / var_ddof0)(X_[:, i], X_[:, m]) * X_[:, m] for the
+ * other i in U. order: device n int32 out. scores: device n * n doubles out or NULL; row s holds
+ * step s's M by original column, -inf for columns ordered before step s, 0 for the last step's
+ * lone candidate.                                                                              */
+int pcg_lingam_pair_scores(pcg_handle *h, const double *X, int64_t T, int64_t m, int64_t ldx, double *D, double *M);
+int pcg_direct_lingam_order(pcg_handle *h, const double *X, int64_t T, int64_t n, int64_t ldx, int32_t *order,
+                            double *scores);
+
 #ifdef __cplusplus
 }
 #endif

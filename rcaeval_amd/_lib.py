@@ -175,6 +175,8 @@ SIGNATURES = [
     ("pcg_chisq_batch", I32, [P, P, I64, I64, P, P, I32, I64, ctypes.c_int, I64, P, P, P]),
     ("pcg_granger", I32, [P, P, I64, I64, I64, ctypes.c_int, P, P, P, P, P, ctypes.POINTER(I64)]),
     ("pcg_granger_guards", I32, [ctypes.POINTER(D), ctypes.POINTER(D), ctypes.POINTER(D)]),
+    ("pcg_lingam_pair_scores", I32, [P, P, I64, I64, I64, P, P]),
+    ("pcg_direct_lingam_order", I32, [P, P, I64, I64, I64, P, P]),
 ]
 
 _lib = None

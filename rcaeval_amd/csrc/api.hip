@@ -174,7 +174,8 @@ extern "C" int pcg_destroy(pcg_handle *h) {
                       &h->deferred, &h->screenq, &h->records, &h->nearbuf, &h->exportbuf, &h->export_xy, &h->diag,
                       &h->colmean, &h->pr_scratch, &h->batch_scratch, &h->chisq_scratch, &h->cblk, &h->lmk,
                       &h->k1_digits, &h->small_sum, &h->batch_up, &h->batch_sum, &h->batch_near,
-                      &h->granger_scratch, &h->granger_work};
+                      &h->granger_scratch, &h->granger_work, &h->lingam_w, &h->lingam_z, &h->lingam_d,
+                      &h->lingam_small};
     for (DevBuf *b : bufs)
         if (b->p) hipFree(b->p);
     PinBuf *pins[] = {&h->ctr_pin, &h->deg_pin, &h->off_pin, &h->cpre_pin, &h->status_pin, &h->small_pin,

@@ -78,6 +78,9 @@ struct pcg_handle {
     DevBuf adj, deg, rm, cpre, binom, ctr, deferred, records, nearbuf, exportbuf, export_xy, diag, colmean,
         pr_scratch, batch_scratch, chisq_scratch;
     DevBuf granger_scratch, granger_work;   // pcg_granger: Z / statistics / exact list; the exact path's designs
+    // pcg_lingam_*: the working copy X_ and the standardized z (n x T each, column-major), one
+    // step's D (n x n), and the column statistics / M / remaining-column lists
+    DevBuf lingam_w, lingam_z, lingam_d, lingam_small;
     DevBuf k1_digits;               // K1 int8 digit / residue planes of the centred X (corr.hip)
     // the (N, n, k, b) a CRT-mode pcg_corr_shard computed h->colmean's column exponents for;
     // pcg_corr_shard_finish refuses to rebuild C from exponents of any other call

@@ -540,6 +540,45 @@ class Engine:
         out["exact_items"] = int(exact.value)
         return out
 
+    def _rows(self, X):
+        """(device tensor, T, n, ldx) of a T x n input: an fp64 tensor already on this device whose
+        rows are contiguous is used in place with its row stride, anything else is uploaded."""
+        torch = _torch()
+        if not (isinstance(X, torch.Tensor) and X.device == self.device and X.dtype == torch.float64 and X.dim() == 2
+                and X.shape[1] >= 1 and X.stride(1) == 1 and X.stride(0) >= X.shape[1]):
+            X = self.to_device(X)
+        if X.dim() != 2:
+            raise ValueError("expected a T x n array")
+        return X, int(X.shape[0]), int(X.shape[1]), int(X.stride(0)) if X.shape[0] > 1 else int(X.shape[1])
+
+    def lingam_pair_scores(self, X):
+        """One DirectLiNGAM search step over all columns of a T x n array
+        (``pcg_lingam_pair_scores``): host arrays ``D`` (n x n, antisymmetric, zero diagonal) and
+        ``M`` (n). n outside 1..4096 or T < 2 raises ``ValueError``."""
+        torch = _torch()
+        Xd, T, n, ldx = self._rows(X)
+        D = torch.empty((n, n), dtype=torch.float64, device=self.device)
+        M = torch.empty(n, dtype=torch.float64, device=self.device)
+        check(self.h, self.lib.pcg_lingam_pair_scores(self.h, ctypes.c_void_p(Xd.data_ptr()), T, n, ldx,
+                                                      ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(M.data_ptr())),
+              "pcg_lingam_pair_scores")
+        return D.cpu().numpy(), M.cpu().numpy()
+
+    def direct_lingam_order(self, X, scores: bool = False):
+        """DirectLiNGAM's causal order of a T x n array (``pcg_direct_lingam_order``): an int32
+        host array of the n column indices; with ``scores`` also the n x n array whose row s is
+        step s's M by original column (-inf once ordered, 0 for the last step's lone candidate)."""
+        torch = _torch()
+        Xd, T, n, ldx = self._rows(X)
+        order = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        S = torch.empty((n, n), dtype=torch.float64, device=self.device) if scores else None
+        check(self.h, self.lib.pcg_direct_lingam_order(self.h, ctypes.c_void_p(Xd.data_ptr()), T, n, ldx,
+                                                       ctypes.c_void_p(order.data_ptr()),
+                                                       ctypes.c_void_p(S.data_ptr()) if scores else None),
+              "pcg_direct_lingam_order")
+        order = order[:n].cpu().numpy()
+        return (order, S.cpu().numpy()) if scores else order
+
     # ------------------------------------------------------------------ K4
     def pagerank_dense(self, A, damping: float = 0.85, n_iter: int = 10, tol: float = 1e-6) -> np.ndarray:
         torch = _torch()

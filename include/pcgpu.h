@@ -471,8 +471,8 @@ int pcg_fisherz_batch(pcg_handle *h, const double *C, int64_t n, int64_t ldc, in
  * [a, b, d, s_0 .. s_{d-1}, pad] (a < b). Per test: the contingency table over the strata of
  * S (empty strata dropped), the chi-square (g_sq = 0) or G-square (g_sq = 1) statistic summed
  * like numpy (bitwise), and its degrees of freedom. stat: device count doubles; df: device count
- * int64; status: device count int32 (0 ok, 3 malformed row or sample, 4 table larger than
- * max_cells). The caller takes p = chi2.sf(stat, df) (p = 1 when df <= 0). Synchronous.  */
+ * int64; status: device count int32 (0 ok, 3 malformed row or sample, 4 table of a
+ * well-formed row larger than max_cells, also when the strata product alone exceeds it). The caller takes p = chi2.sf(stat, df) (p = 1 when df <= 0). Synchronous.  */
 int pcg_chisq_batch(pcg_handle *h, const int32_t *data, int64_t N, int64_t n, const int32_t *card,
                     const int32_t *tests, int32_t stride, int64_t count, int g_sq, int64_t max_cells,
                     double *stat, int64_t *df, int32_t *status);

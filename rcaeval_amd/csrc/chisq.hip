@@ -101,7 +101,11 @@ __global__ __launch_bounds__(CHI_BLOCK) void k_chisq(const int32_t *data, int64_
             P.a = row[0]; P.b = row[1]; P.d = row[2];
             int bad = (P.d < 0 || P.d > PCG_MAX_LEVEL_DEPTH || P.d + 3 > stride || P.a < 0 || P.b < 0 || P.a >= n ||
                        P.b >= n || P.a == P.b);
+            // a malformed row is status 3 whatever its size; a well-formed one whose table (or
+            // whose strata product alone) exceeds max_cells is status 4. Once over, cS stops
+            // growing (no int64 overflow) and the remaining entries are still validated.
             int64_t cS = 1;
+            int over = 0;
             for (int q = 0; !bad && q < P.d; ++q) {
                 const int s = row[3 + q];
                 bad |= (s < 0 || s >= n || s == P.a || s == P.b);
@@ -110,16 +114,19 @@ __global__ __launch_bounds__(CHI_BLOCK) void k_chisq(const int32_t *data, int64_
                 P.cum[q] = cS;
                 const int c = card[s];
                 bad |= c < 1;
-                cS *= c;
-                bad |= cS > max_cells;
+                if (bad) break;
+                if (!over) cS *= c;
+                over |= cS > max_cells;
             }
             if (!bad) {
                 P.cS = cS;
                 P.cX = card[P.a];
                 P.cY = card[P.b];
                 bad |= P.cX < 1 || P.cY < 1;
-                P.cells = P.cS * P.cX * P.cY;
-                if (!bad && P.cells > max_cells) bad = 2;
+                // cS <= max_cells <= 2^26 here unless over, cards < 2^31: divide, do not multiply
+                if (!bad && !over) over = P.cX > max_cells / cS || P.cX * cS > max_cells / P.cY;
+                P.cells = over ? 0 : P.cS * P.cX * P.cY;
+                if (!bad && over) bad = 2;
             }
             P.bad = bad;
             bad_sample = 0;

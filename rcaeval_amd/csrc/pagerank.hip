@@ -3,7 +3,9 @@
 // (1) scikit-network 0.31.0 PageRank(damping_factor=0.85, solver='piteration', n_iter=10,
 //     tol=1e-6).fit_transform(A) [U], as called at RCAEval/e2e/pc_pagerank.py:31-32 and
 //     RCAEval/graph_heads/page_rank.py:85-89. Restated semantics:
-//       out_deg = A @ 1 (bool);  a = (d * normalize(A, p=1)).T  (CSR, rows sorted by column)
+//       out_deg = (A @ 1).astype(bool): the signed row sum, summed sequentially in storage order
+//       (signed weights that cancel exactly make the row dangling); normalize divides by sum |a|
+//       a = (d * normalize(A, p=1)).T  (CSR, rows sorted by column)
 //       b = (1 - d * out_deg) * seeds,  seeds = 1/m
 //       scores = b; repeat n_iter: s_ = a @ scores + b * sum(scores); s_ /= sum(s_)
 //                    if ||scores - s_||_1 < tol: break  else scores = s_
@@ -139,14 +141,16 @@ __global__ __launch_bounds__(PR_THREADS) void k_pagerank(const double *A, int m,
     if (tid == 0) pw_plan(L, m);
     // out-degree sums (row sums in column order) and their pseudo-inverse
     for (int j = tid; j < m; j += blockDim.x) {
-        double rs = 0.0;
+        // rs = sum |a| (normalize's l1 norm), sg = the signed sum A @ 1 whose truth value is
+        // out_deg: a row whose entries cancel exactly is dangling in b and still normalised
+        double rs = 0.0, sg = 0.0;
         if (A) {
-            for (int k = 0; k < m; ++k) rs += fabs(A[(int64_t)j * lda + k]);
+            for (int k = 0; k < m; ++k) { const double a = A[(int64_t)j * lda + k]; rs += fabs(a); sg += a; }
         } else {
-            for (int q = indptr[j]; q < indptr[j + 1]; ++q) rs += fabs(data[q]);
+            for (int q = indptr[j]; q < indptr[j + 1]; ++q) { const double a = data[q]; rs += fabs(a); sg += a; }
         }
         inv[j] = rs != 0.0 ? 1.0 / rs : 0.0;
-        b[j] = (1.0 - damping * (rs != 0.0 ? 1.0 : 0.0)) * (1.0 / (double)m);
+        b[j] = (1.0 - damping * (sg != 0.0 ? 1.0 : 0.0)) * (1.0 / (double)m);
     }
     __syncthreads();
     // transposed CSR of (d * D^-1 A): row i of a lists j ascending with A[j, i] != 0

@@ -153,18 +153,46 @@ class Engine:
         arr = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
         return torch.from_numpy(arr).to(self.device)
 
+    def _strided(self, a):
+        """True for an fp64 2-d tensor already on this device whose rows are contiguous
+        (``stride(1) == 1``, ``stride(0) >= ncols``): the ABI takes it in place with its row
+        stride as the leading dimension."""
+        torch = _torch()
+        return (isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == torch.float64
+                and a.dim() == 2 and a.shape[1] >= 1 and a.stride(1) == 1 and a.stride(0) >= a.shape[1])
+
+    def _ld(self, a):
+        """(device tensor, leading dimension) of a 2-d input: a row-strided device view is used in
+        place (``_strided``), host arrays and every other tensor are uploaded / made contiguous."""
+        if not self._strided(a):
+            a = self.to_device(a)
+        if a.dim() != 2:
+            raise ValueError("expected a 2-d array")
+        return a, (int(a.stride(0)) if a.shape[0] > 1 else int(a.shape[1]))
+
+    def _out_view(self, out, n: int):
+        """(n x n fp64 device tensor, ldc) for a correlation result: a fresh contiguous tensor, or
+        the caller's row-strided device view ``out`` written in place (its padding untouched)."""
+        torch = _torch()
+        if out is None:
+            return torch.empty((n, n), dtype=torch.float64, device=self.device), n
+        if not self._strided(out) or tuple(out.shape) != (n, n):
+            raise ValueError(f"out= must be a {n} x {n} float64 view on {self.device} with contiguous rows")
+        return out, (int(out.stride(0)) if n > 1 else n)
+
     def sync(self):
         _torch().cuda.synchronize(self.device)
 
     # ------------------------------------------------------------------ K1
-    def corr(self, X) -> "object":
-        """``np.corrcoef(X.T)`` of an N x n array on the GPU; returns an n x n fp64 tensor."""
-        torch = _torch()
-        Xd = self.to_device(X)
+    def corr(self, X, out=None) -> "object":
+        """``np.corrcoef(X.T)`` of an N x n array on the GPU; returns an n x n fp64 tensor.
+        A row-strided fp64 device view of X is read in place (``ldx`` = its row stride);
+        ``out``: an n x n device view to write C into (``ldc`` = its row stride), returned."""
+        Xd, ldx = self._ld(X)
         N, n = Xd.shape
-        C = torch.empty((n, n), dtype=torch.float64, device=self.device)
-        check(self.h, self.lib.pcg_corr(self.h, ctypes.c_void_p(Xd.data_ptr()), N, n, n,
-                                        ctypes.c_void_p(C.data_ptr()), n), "pcg_corr")
+        C, ldc = self._out_view(out, n)
+        check(self.h, self.lib.pcg_corr(self.h, ctypes.c_void_p(Xd.data_ptr()), N, n, ldx,
+                                        ctypes.c_void_p(C.data_ptr()), ldc), "pcg_corr")
         return C
 
     def corr_shard(self, X, rank: int, world: int):
@@ -295,7 +323,7 @@ class Engine:
         ``banned``: n x n mask of pairs removed at the end of depth 0 (background knowledge,
         ``rcaeval_amd.background.banned_pairs``)."""
         torch = _torch()
-        Cd = self.to_device(C)
+        Cd, ldc = self._ld(C)
         n = Cd.shape[0]
         rl = torch.empty((n, n), dtype=torch.int8, device=self.device)
         if record_capacity:
@@ -308,7 +336,7 @@ class Engine:
         self._sep_arm(n)
         try:
             ev0.record()
-            rc = self.lib.pcg_skeleton(self.h, ctypes.c_void_p(Cd.data_ptr()), n, n, int(N), float(alpha),
+            rc = self.lib.pcg_skeleton(self.h, ctypes.c_void_p(Cd.data_ptr()), n, ldc, int(N), float(alpha),
                                        int(max_depth), int(flags), ctypes.c_void_p(rl.data_ptr()),
                                        ctypes.byref(st))
             ev1.record()
@@ -323,12 +351,13 @@ class Engine:
         return out
 
     def corr_skeleton(self, X, alpha: float = 0.05, max_depth: int = -1, flags: int = 0, record_capacity: int = 0,
-                      banned=None):
-        """K1 + stable skeleton in one C call (``pcg_pc_skeleton``); returns (SkeletonOut, C)."""
+                      banned=None, out=None):
+        """K1 + stable skeleton in one C call (``pcg_pc_skeleton``); returns (SkeletonOut, C).
+        X and ``out`` as in ``corr``."""
         torch = _torch()
-        Xd = self.to_device(X)
+        Xd, ldx = self._ld(X)
         N, n = Xd.shape
-        C = torch.empty((n, n), dtype=torch.float64, device=self.device)
+        C, ldc = self._out_view(out, n)
         rl = torch.empty((n, n), dtype=torch.int8, device=self.device)
         if record_capacity:
             check(self.h, self.lib.pcg_set_capacity(self.h, int(record_capacity), 0), "pcg_set_capacity")
@@ -339,8 +368,8 @@ class Engine:
         self._sep_arm(n)
         try:
             ev0.record()
-            rc = self.lib.pcg_pc_skeleton(self.h, ctypes.c_void_p(Xd.data_ptr()), N, n, n,
-                                          ctypes.c_void_p(C.data_ptr()), n, float(alpha), int(max_depth), int(flags),
+            rc = self.lib.pcg_pc_skeleton(self.h, ctypes.c_void_p(Xd.data_ptr()), N, n, ldx,
+                                          ctypes.c_void_p(C.data_ptr()), ldc, float(alpha), int(max_depth), int(flags),
                                           ctypes.c_void_p(rl.data_ptr()), ctypes.byref(st))
             ev1.record()
         finally:
@@ -382,8 +411,12 @@ class Engine:
             Nl = [int(Ns)] * B if np.isscalar(Ns) else [int(v) for v in Ns]
             if len(Nl) != B:
                 raise ValueError("skeleton_batch: one N per case")
-        # one packed device buffer per kind
-        if all(isinstance(a, np.ndarray) for a in arrs):
+        # one packed device buffer per kind — unless every case is a row-strided device view
+        # (_strided): the cases then point at the views with their own leading dimensions
+        views = all(self._strided(a) for a in arrs)
+        if views:
+            flat = None
+        elif all(isinstance(a, np.ndarray) for a in arrs):
             # packed in a page-locked staging buffer kept by the engine (grow-only), one H2D copy;
             # the copy is blocking, so the buffer is free again when the next batch packs into it
             total = sum(a.size for a in arrs)
@@ -403,18 +436,27 @@ class Engine:
         in_off = np.concatenate([[0], np.cumsum([a.shape[0] * a.shape[1] for a in arrs])])
         sq_off = np.concatenate([[0], np.cumsum(sq)])
         row_off = np.concatenate([[0], np.cumsum(rows_cap)])
+        # (from_data: the batched K1's C stays packed, also for views)
         Call = torch.empty(int(sq_off[-1]), dtype=torch.float64, device=self.device) if from_data else flat
         rl = torch.empty(int(sq_off[-1]), dtype=torch.int8, device=self.device)
         xy = torch.empty((int(row_off[-1]), 2), dtype=torch.int32, device=self.device)
         bits = torch.empty((int(row_off[-1]), 1), dtype=torch.int64, device=self.device)
         cases = (_lib.PcgCase * B)()
-        pin, pC, prl, pxy, pbits = flat.data_ptr(), Call.data_ptr(), rl.data_ptr(), xy.data_ptr(), bits.data_ptr()
+        prl, pxy, pbits = rl.data_ptr(), xy.data_ptr(), bits.data_ptr()
+        pin = None if views else flat.data_ptr()
+        pC = None if Call is None else Call.data_ptr()
         for i in range(B):
             c = cases[i]
-            c.X = pin + 8 * int(in_off[i]) if from_data else None
-            c.N, c.n, c.ldx = Nl[i], ns[i], ns[i]
-            c.C = pC + 8 * int(sq_off[i])
-            c.ldc = ns[i]
+            c.N, c.n = Nl[i], ns[i]
+            if views:
+                ld = int(arrs[i].stride(0)) if arrs[i].shape[0] > 1 else ns[i]
+                c.X, c.ldx = (arrs[i].data_ptr(), ld) if from_data else (None, ns[i])
+                c.C, c.ldc = (pC + 8 * int(sq_off[i]), ns[i]) if from_data else (arrs[i].data_ptr(), ld)
+            else:
+                c.X = pin + 8 * int(in_off[i]) if from_data else None
+                c.ldx = ns[i]
+                c.C = pC + 8 * int(sq_off[i])
+                c.ldc = ns[i]
             c.removed_level = prl + int(sq_off[i])
             c.sep_xy = pxy + 8 * int(row_off[i])
             c.sep_bits = pbits + 8 * int(row_off[i])
@@ -439,7 +481,7 @@ class Engine:
             out.rc = int(r.rc)
             out._host = {"rl": rl_h[s0:s0 + n * n].reshape(n, n), "xy": xy_h[r0:r0 + rows],
                          "bits": bits_h[r0:r0 + rows]}
-            out.extra["C"] = Call[s0:s0 + n * n].view(n, n)
+            out.extra["C"] = arrs[i] if Call is None else Call[s0:s0 + n * n].view(n, n)
             outs.append(out)
         return outs
 
@@ -491,14 +533,14 @@ class Engine:
         """Fisher-z p of canonical rows ``[a, b, d, s_0..s_{d-1}, pad]`` (int32, count x stride)
         on the device correlation ``C``; returns (p float64, status int32) host arrays."""
         torch = _torch()
-        Cd = self.to_device(C)
+        Cd, ldc = self._ld(C)
         n = Cd.shape[0]
         rows = np.ascontiguousarray(rows, dtype=np.int32)
         count, stride = rows.shape
         t = torch.from_numpy(rows).to(self.device)
         p = torch.empty(count, dtype=torch.float64, device=self.device)
         st = torch.empty(count, dtype=torch.int32, device=self.device)
-        check(self.h, self.lib.pcg_fisherz_batch(self.h, ctypes.c_void_p(Cd.data_ptr()), n, n, int(N),
+        check(self.h, self.lib.pcg_fisherz_batch(self.h, ctypes.c_void_p(Cd.data_ptr()), n, ldc, int(N),
                                                  ctypes.c_void_p(t.data_ptr()), int(stride), int(count),
                                                  ctypes.c_void_p(p.data_ptr()), ctypes.c_void_p(st.data_ptr())),
               "pcg_fisherz_batch")
@@ -527,13 +569,13 @@ class Engine:
         [i, j, L - 1] = column j causing column i at lag L, and ``exact_items``, the number of
         items the exact path computed. ``T <= 3 * maxlag + 1`` raises ``ValueError``."""
         torch = _torch()
-        Xd = self.to_device(X)
+        Xd, ldx = self._ld(X)
         T, n = Xd.shape
         shape = (n, n, int(maxlag))
         f = [torch.empty(shape, dtype=torch.float64, device=self.device) for _ in range(3)]
         k = [torch.empty(shape, dtype=torch.int32, device=self.device) for _ in range(2)]
         exact = ctypes.c_int64()
-        check(self.h, self.lib.pcg_granger(self.h, ctypes.c_void_p(Xd.data_ptr()), int(T), int(n), int(n), int(maxlag),
+        check(self.h, self.lib.pcg_granger(self.h, ctypes.c_void_p(Xd.data_ptr()), int(T), int(n), ldx, int(maxlag),
                                            *(ctypes.c_void_p(t.data_ptr()) for t in f + k), ctypes.byref(exact)),
               "pcg_granger")
         out = {name: t.cpu().numpy() for name, t in zip(("ssr_r", "ssr_u", "tss", "rank", "status"), f + k)}
@@ -543,9 +585,7 @@ class Engine:
     def _rows(self, X):
         """(device tensor, T, n, ldx) of a T x n input: an fp64 tensor already on this device whose
         rows are contiguous is used in place with its row stride, anything else is uploaded."""
-        torch = _torch()
-        if not (isinstance(X, torch.Tensor) and X.device == self.device and X.dtype == torch.float64 and X.dim() == 2
-                and X.shape[1] >= 1 and X.stride(1) == 1 and X.stride(0) >= X.shape[1]):
+        if not self._strided(X):
             X = self.to_device(X)
         if X.dim() != 2:
             raise ValueError("expected a T x n array")
@@ -582,10 +622,10 @@ class Engine:
     # ------------------------------------------------------------------ K4
     def pagerank_dense(self, A, damping: float = 0.85, n_iter: int = 10, tol: float = 1e-6) -> np.ndarray:
         torch = _torch()
-        Ad = self.to_device(A)
+        Ad, lda = self._ld(A)
         m = Ad.shape[0]
         out = torch.empty(m, dtype=torch.float64, device=self.device)
-        check(self.h, self.lib.pcg_pagerank_dense(self.h, ctypes.c_void_p(Ad.data_ptr()), m, m, float(damping),
+        check(self.h, self.lib.pcg_pagerank_dense(self.h, ctypes.c_void_p(Ad.data_ptr()), m, lda, float(damping),
                                                   int(n_iter), float(tol), ctypes.c_void_p(out.data_ptr())),
               "pcg_pagerank_dense")
         return out.cpu().numpy()
@@ -607,11 +647,11 @@ class Engine:
 
     def random_walk_counts(self, P, start: int, num_loop: int, state: int, inc: int) -> np.ndarray:
         torch = _torch()
-        Pd = self.to_device(P)
+        Pd, ldp = self._ld(P)
         m = Pd.shape[0]
         counts = torch.empty(m, dtype=torch.int64, device=self.device)
         mask = (1 << 64) - 1
-        check(self.h, self.lib.pcg_random_walk(self.h, ctypes.c_void_p(Pd.data_ptr()), m, m, int(start),
+        check(self.h, self.lib.pcg_random_walk(self.h, ctypes.c_void_p(Pd.data_ptr()), m, ldp, int(start),
                                                int(num_loop), (state >> 64) & mask, state & mask,
                                                (inc >> 64) & mask, inc & mask,
                                                ctypes.c_void_p(counts.data_ptr())),

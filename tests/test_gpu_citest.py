@@ -44,6 +44,58 @@ def test_fisherz_batch_matches_oracle_all_depths(eng, seed):
     assert fisherz.p_close(p, ref).all()
 
 
+def test_fisherz_batch_more_rows_than_lanes(eng):
+    """40 000 rows on at most 32768 lanes: lanes 0..7231 take a second row (t + 32768). Every row
+    is compared with the oracle (one call per distinct test: the rows cycle through 4096 of
+    them, so rows t and t + 32768 carry the same test and must give the same bits), with
+    malformed rows (status 3) and rows through a zeroed row and column of C (status 1) on both
+    sides of index 32768; every status is checked."""
+    rng = np.random.default_rng(40)
+    n, N, stride, count, lanes = 40, 900, 9, 40_000, 32768
+    X = synth.gaussian_sem(n, N, seed=52, w_low=0.3, w_high=0.9)
+    C = np.corrcoef(X.T)
+    Z = 5
+    C[Z, :] = 0.0
+    C[:, Z] = 0.0
+    live = np.delete(np.arange(n), Z)
+    pool = []
+    for k in range(4096):
+        v = rng.choice(live, size=k % 7 + 2, replace=False)
+        a, b = sorted(int(t) for t in v[:2])
+        pool.append((a, b, sorted(int(t) for t in v[2:])))
+    pool_rows = _rows(pool, stride)
+    rows = pool_rows[np.arange(count) % len(pool)].copy()
+    want_st = np.zeros(count, np.int32)
+    malformed = [[2, 2, 0], [0, n, 0], [-1, 3, 0], [0, 1, 1, 1], [0, 1, 2, 3, 0], [0, 1, 7, 2, 3, 4, 6, 7, 8],
+                 [0, 1, -1], [0, 1, 1, n]]
+    at3 = [3, 100, 7231, 7232, lanes - 1, lanes, lanes + 1, lanes + 3, 36000, count - 1, 20000, 32800]
+    for k, t in enumerate(at3):
+        r = malformed[k % len(malformed)]
+        rows[t] = -1
+        rows[t, :len(r)] = r
+        want_st[t] = 3
+    singular = [(0, 1, [Z]), (2, Z, []), (3, 4, [1, Z, 9]), (Z, 7, [2, 3]), (1, 2, [3, 4, Z, 6, 7, 8])]
+    at1 = [7, 5000, 7230, lanes - 2, lanes + 7, lanes + 5000, 39000, count - 2]
+    for k, t in enumerate(at1):
+        rows[t] = _rows([singular[k % len(singular)]], stride)[0]
+        want_st[t] = 1
+    for a, b, S in singular:
+        with pytest.raises(ValueError):
+            fisherz.pvalue(C, N, a, b, S)
+    p, st = eng.fisherz_batch(C, N, rows)
+    np.testing.assert_array_equal(st, want_st)
+    ok = want_st == 0
+    assert np.isnan(p[~ok]).all()
+    ref = np.array([fisherz.pvalue(C, N, a, b, S) for (a, b, S) in pool])
+    full = ref[np.arange(count) % len(pool)]
+    close = fisherz.p_close(p[ok], full[ok])
+    assert close.all(), np.flatnonzero(ok)[~close][:5]
+    t = np.arange(count - lanes)
+    t = t[ok[t] & ok[t + lanes]]
+    assert len(t) > 7000
+    np.testing.assert_array_equal(p[t], p[t + lanes])
+
+
 def test_fisherz_batch_errors(eng):
     n = 8
     X = synth.gaussian_sem(n, 60, seed=4)

@@ -44,6 +44,26 @@ def test_pagerank_sizes_vs_oracle(m, n_iter):
     np.testing.assert_array_equal(PageRank(n_iter=n_iter).fit_transform(sparse.csr_matrix(A)), ref)
 
 
+@pytest.mark.parametrize("m", [50, 300])
+def test_pagerank_signed_weights_vs_oracle(m):
+    """Signed weights through the public PageRank class: rows of non-zero entries whose signed
+    sum is exactly 0 are dangling in the reference (out_deg = (A @ 1).astype(bool)) although
+    normalize divides them by sum |a|; rows that cancel only up to rounding make the flag depend
+    on the order of the signed sum (dense: columns ascending; CSR: storage order). Dense and CSR
+    entries, bitwise the scipy/numpy oracle."""
+    from scipy import sparse
+    from oracle import pagerank as opr
+    from rcaeval_amd.graph_heads.page_rank import PageRank
+    from tests_support import signed_pagerank_matrix
+    A, cancel, zero = signed_pagerank_matrix(m, m)
+    sg = sparse.csr_matrix(A).dot(np.ones(m))
+    assert len(cancel) >= 3 and (np.count_nonzero(A[cancel], axis=1) >= 2).all() and (sg[cancel] == 0).all()
+    assert len(zero) >= 3 and not A[zero].any()
+    ref = opr.pagerank(A)
+    np.testing.assert_array_equal(PageRank().fit_transform(A), ref)
+    np.testing.assert_array_equal(PageRank().fit_transform(sparse.csr_matrix(A)), ref)
+
+
 def test_pagerank_csr_refuses_understated_nnz_and_bad_columns():
     from scipy import sparse
     from rcaeval_amd._lib import PcgError
@@ -86,6 +106,71 @@ def test_random_walk_serial_path_matches_numpy():
     st = np.random.default_rng(0).bit_generator.state["state"]
     got = get_engine(0).random_walk_counts(P, 3, 500, st["state"], st["inc"])
     np.testing.assert_array_equal(got, orw.walk_counts(P, 3, 500))
+
+
+def _tied_column(m, seed):
+    """A probability column with about 40% exact zeros (ties in the cdf), p[0] and p[m-1] among them."""
+    rng = np.random.default_rng(seed)
+    p = rng.random(m)
+    p[rng.random(m) < 0.4] = 0.0
+    p[0] = p[m - 1] = 0.0
+    return p / p.sum()
+
+
+def _vector_counts(p, u):
+    """Generator.choice(p=...) for given uniforms u, vectorised: cdf = cumsum(p); cdf /= cdf[-1];
+    searchsorted(cdf, u, 'right')."""
+    cdf = np.cumsum(p)
+    cdf /= cdf[-1]
+    return np.bincount(cdf.searchsorted(u, "right"), minlength=len(p))
+
+
+def test_random_walk_parallel_path_long_jump_ahead_and_ties():
+    """Identical columns take k_rw_parallel: m = 300 is two blocks of k_rw_cdf, 70 000 draws jump
+    PCG64 ahead by up to 17 bits, the column's exact zeros are ties in the cdf that no draw may
+    land on. Reference: numpy's own generator through the vectorised form of choice(), which
+    equals the walk restatement on its first 2000 draws (asserted). Also from a generator that
+    is not fresh (12345 doubles consumed)."""
+    from oracle import random_walk as orw
+    from rcaeval_amd.engine import get_engine
+    m, num_loop = 300, 70_000
+    p = _tied_column(m, 17)
+    zeros = p == 0.0
+    assert 0.3 * m < zeros.sum() < 0.5 * m and zeros[0] and zeros[-1]
+    P = np.tile(p[:, None], (1, m))
+    np.testing.assert_array_equal(_vector_counts(p, np.random.default_rng(0).random(2000)),
+                                  orw.walk_counts(P, 0, 2000))
+    eng = get_engine(0)
+    st = np.random.default_rng(0).bit_generator.state["state"]
+    got = eng.random_walk_counts(P, 0, num_loop, st["state"], st["inc"])
+    assert got.sum() == num_loop and not got[zeros].any()
+    np.testing.assert_array_equal(got, _vector_counts(p, np.random.default_rng(0).random(num_loop)))
+    rng = np.random.default_rng(0)
+    rng.random(12345)
+    st = rng.bit_generator.state["state"]
+    got = eng.random_walk_counts(P, 5, num_loop, st["state"], st["inc"])
+    assert got.sum() == num_loop and not got[zeros].any()
+    np.testing.assert_array_equal(got, _vector_counts(p, rng.random(num_loop)))
+
+
+def test_random_walk_serial_path_sparse_columns():
+    """k_rw_serial on m = 300 (two blocks of k_rw_cdf): every column has 3-6 non-zeros and a zero
+    diagonal, so each cdf is mostly ties; 2000 steps against numpy's choice."""
+    from oracle import random_walk as orw
+    from rcaeval_amd.engine import get_engine
+    rng = np.random.default_rng(23)
+    m = 300
+    P = np.zeros((m, m))
+    for c in range(m):
+        rows = rng.choice(np.delete(np.arange(m), c), size=int(rng.integers(3, 7)), replace=False)
+        P[rows, c] = rng.random(len(rows)) + 0.05
+    P /= P.sum(0, keepdims=True)
+    assert (np.diag(P) == 0).all() and ((P != 0).sum(0) >= 3).all() and ((P != 0).sum(0) <= 6).all()
+    st = np.random.default_rng(0).bit_generator.state["state"]
+    got = get_engine(0).random_walk_counts(P, 7, 2000, st["state"], st["inc"])
+    want = orw.walk_counts(P, 7, 2000)
+    assert got.sum() == 2000
+    np.testing.assert_array_equal(got, want)
 
 
 def _oracle_pipeline(df, dataset, head, alpha=0.05, sli=None):

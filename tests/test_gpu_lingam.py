@@ -89,6 +89,32 @@ def test_pair_scores_match_the_restatement(gen, T, n):
         _check_scores(f"{gen} T={T} n={n} X_ at step {s}", snaps[s][:, U])
 
 
+@pytest.mark.parametrize("T,m", [(300, 70), (150, 130)])
+def test_pair_scores_rows_wider_than_a_wavefront(T, m):
+    """k_lingam_reduce's 64 lanes stride over a row of D: m = 70 gives lanes 0..5 a second
+    element, m = 130 every lane a third pass. (T keeps the float64 + long double restatement at
+    about ten seconds on the host.) Same tolerances as above."""
+    _check_scores(f"laplace T={T} m={m}", lr.GENERATORS["laplace"](T, m, 0))
+
+
+def test_order_wider_than_the_argmax_block():
+    """n = 260: block_argmax's 256 threads stride over M (threads 0..3 take a second candidate)
+    and k_lingam_reduce runs five passes per row. The restatement is too slow at this size, so
+    the order is checked against the engine's own scores: a permutation, each step's choice
+    np.argmax of that step's row, row 0 bit for bit the single step's M, ordered columns -inf."""
+    T, n = 300, 260
+    X = lr.GENERATORS["laplace"](T, n, 0)
+    eng = _engine()
+    order, S = eng.direct_lingam_order(X.copy(), scores=True)
+    assert order.dtype == np.int32 and sorted(order.tolist()) == list(range(n))
+    assert S.shape == (n, n) and not np.isnan(S).any()
+    np.testing.assert_array_equal(S[0], eng.lingam_pair_scores(X.copy())[1])
+    for s in range(n):
+        assert int(order[s]) == int(np.argmax(S[s])), s
+        assert np.isneginf(S[s, order[:s]]).all() and np.isfinite(S[s, order[s:]]).all(), s
+    assert S[n - 1, order[n - 1]] == 0
+
+
 @pytest.mark.parametrize("T,n", SHAPES)
 @pytest.mark.parametrize("eps", [1e-3, 1e-6, 1e-9])
 def test_pair_scores_on_collinear_columns(eps, T, n):

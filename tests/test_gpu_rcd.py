@@ -22,9 +22,9 @@ def _rows(rng, n, count, dmax):
     return np.array(rows, np.int32), keys
 
 
-@pytest.mark.parametrize("n,N,cmax,dmax,gsq", [(8, 1500, 5, 3, False), (12, 4000, 3, 4, False), (6, 800, 5, 2, True),
-                                               (7, 3000, 6, 4, False), (9, 20000, 8, 4, False)])
-def test_chisq_batch_matches_oracle(n, N, cmax, dmax, gsq):
+def _chisq_case(n, N, cmax, dmax):
+    """The fixture of test_chisq_batch_matches_oracle: cards, codes, 200 canonical rows, their keys
+    and device copies (a function of the four parameters alone)."""
     import torch
     from rcaeval_amd.engine import get_engine
     rng = np.random.default_rng(n * N)
@@ -36,6 +36,13 @@ def test_chisq_batch_matches_oracle(n, N, cmax, dmax, gsq):
     cd = torch.from_numpy(card.astype(np.int32)).to(eng.device)
     rows, keys = _rows(rng, n, 200, dmax)
     cells = max(int(np.prod(card[S + [a, b]])) for a, b, S in keys)
+    return eng, card, codes, data, cd, rows, keys, cells
+
+
+@pytest.mark.parametrize("n,N,cmax,dmax,gsq", [(8, 1500, 5, 3, False), (12, 4000, 3, 4, False), (6, 800, 5, 2, True),
+                                               (7, 3000, 6, 4, False), (9, 20000, 8, 4, False)])
+def test_chisq_batch_matches_oracle(n, N, cmax, dmax, gsq):
+    eng, card, codes, data, cd, rows, keys, cells = _chisq_case(n, N, cmax, dmax)
     stat, df, st = eng.chisq_batch(data, cd, N, n, rows, gsq, cells)
     assert (st == 0).all()
     for r, (a, b, S) in enumerate(keys):
@@ -44,6 +51,198 @@ def test_chisq_batch_matches_oracle(n, N, cmax, dmax, gsq):
         if gsq:   # the device log may differ from glibc's in the last bit
             assert abs(stat[r] - want) <= 1e-13 * abs(want), (r, stat[r], want)
         else:     # numpy's blocked pairwise order: bitwise
+            assert stat[r] == want, (r, stat[r], want)
+
+
+def _gsq_abs_terms(dataSXY, cardSXY):
+    """sum |2 c log(div)| over the cells of chisq_or_gsq_stat's G-square, with c and div built
+    exactly as oracle/chisq.py builds them."""
+    cardSXY = np.asarray(cardSXY, dtype=np.int64)
+    cardX, cardY = cardSXY[-2:]
+    if len(cardSXY) == 2:
+        xy = np.bincount(dataSXY[0] * cardY + dataSXY[1], minlength=cardX * cardY).reshape((cardX, cardY))
+        c = xy[None]
+        e = (np.outer(np.sum(xy, axis=1), np.sum(xy, axis=0)) / dataSXY.shape[1])[None]
+    else:
+        cardS = int(np.prod(cardSXY[:-2]))
+        cum = np.ones_like(cardSXY)
+        cum[1:] = np.cumprod(cardSXY[:-1])
+        idx = np.dot(cum[None], dataSXY)[0]
+        T = np.bincount(idx, minlength=cardS * cardX * cardY).reshape((cardY, cardX, cardS))
+        T = np.transpose(T, (2, 1, 0))
+        Sm = np.sum(T, axis=(1, 2))
+        keep = Sm != 0
+        Sm, T = Sm[keep], T[keep]
+        c = T
+        e = np.sum(T, axis=2)[:, :, None] * np.sum(T, axis=1)[:, None, :] / Sm[:, None, None]
+    e1 = np.copy(e)
+    e1[e == 0] = 1
+    div = np.divide(c, e1)
+    div[div == 0] = 1
+    return float(np.sum(np.abs(2 * (c * np.log(div))))), c.size
+
+
+def test_gsq_on_the_global_table():
+    """G-square where the table and the term array leave LDS and one numpy summation block: the
+    (9, 20000, 8, 4) fixture has tables of up to 94080 cells (> 8192), so counts and terms live in
+    the block's global scratch and the statistic is summed over several 8192-element blocks.
+    sum |term| / |sum term| reaches 124 here, so the bound is on the terms, not on the result:
+    |got - want| <= 4 * 2^-52 * sum |2 c log(div)| — the device log within one ulp plus the
+    product's rounding is about 1.5 * 2^-52 per term, the summation order is numpy's; the factor 4
+    is margin on the assumed 1-ulp log. Prints the worst |got - want| / (2^-52 sum |term|)."""
+    n, N = 9, 20000
+    eng, card, codes, data, cd, rows, keys, cells = _chisq_case(n, N, 8, 4)
+    assert cells > 8192
+    stat, df, st = eng.chisq_batch(data, cd, N, n, rows, True, cells)
+    assert (st == 0).all()
+    worst, big, fails = 0.0, 0, []
+    for r, (a, b, S) in enumerate(keys):
+        sxy = codes[:, S + [a, b]].T
+        want, wdf = och.chisq_or_gsq_stat(sxy, card[S + [a, b]], True)
+        mag, nterms = _gsq_abs_terms(sxy, card[S + [a, b]])
+        big += nterms > 8192
+        assert df[r] == wdf
+        ratio = abs(stat[r] - want) / (2.0 ** -52 * mag) if mag else float(stat[r] != want)
+        worst = max(worst, ratio)
+        if not ratio <= 4.0:
+            fails.append((r, stat[r], want, ratio))
+    print(f"gsq global table: worst |got - want| / (2^-52 sum|term|) = {worst:.3f} (limit 4); "
+          f"{big} of {len(keys)} tests with more than 8192 terms")
+    assert big > 0
+    assert not fails, fails[:5]
+
+
+# cards of the status-mix fixture: var 1 has a single level, var 5 holds an out-of-range sample
+_MIX_CARD = np.array([4, 1, 4, 4, 4, 3, 2, 4])
+_MIX_BAD_VAR = 5
+
+
+def _mix_rows(rng, count, stride, max_cells):
+    """Rows and expected status (-1 = not pinned) for test_chisq_block_reuse_and_status_mix."""
+    n, card = len(_MIX_CARD), _MIX_CARD
+    fours = [0, 2, 3, 4, 7]
+
+    def canon(a, b, S):
+        return [a, b, len(S)] + list(S) + [-1] * (stride - 3 - len(S))
+
+    def valid():
+        while True:
+            d = int(rng.integers(0, 4))
+            v = rng.choice(np.delete(np.arange(n), _MIX_BAD_VAR), size=d + 2, replace=False)
+            a, b = sorted(v[:2].tolist())
+            S = sorted(v[2:].tolist())
+            if int(np.prod(card[S + [a, b]])) <= max_cells:
+                return canon(a, b, S), 0
+
+    def over_strata():        # five card-4 variables in S: 4^5 = 1024 > 256 before x and y count
+        return canon(1, 6, rng.permutation(fours).tolist()), 4
+
+    def over_table():         # strata fit (at most 64 cells), the full table does not
+        v = rng.choice(fours + [6], size=5, replace=False).tolist()     # 4^5 = 1024 or 4^4 * 2 = 512
+        a, b = sorted(v[:2])
+        return canon(a, b, v[2:]), 4
+
+    def malformed():
+        k = int(rng.integers(0, 6))
+        r = [[2, 2, 0], [0, n, 0], [-1, 3, 0], [0, 1, 1, 1], [0, 2, 2, 3, 0], [0, 1, 1, n]][k]
+        return r + [-1] * (stride - len(r)), 3
+
+    def bad_sample():         # touches the variable with an out-of-range sample, table fits
+        while True:
+            d = int(rng.integers(0, 3))
+            v = rng.choice(np.delete(np.arange(n), _MIX_BAD_VAR), size=d + 1, replace=False).tolist()
+            pos = int(rng.integers(0, d + 2))
+            v.insert(pos, _MIX_BAD_VAR)
+            a, b = sorted(v[:2])
+            if int(np.prod(card[v])) <= max_cells:
+                return canon(a, b, sorted(v[2:])), 3
+
+    refused = [over_strata, over_table, malformed, bad_sample]
+    rows = np.zeros((count, stride), np.int32)
+    want = np.zeros(count, np.int32)
+    grid = 4096
+    for t in range(count):
+        b = t % grid
+        if b < count - grid:      # a block that runs two tests: refused then valid, or valid then refused
+            first_refused = (b // len(refused)) % 2 == 0
+            if b % 9 == 8:
+                make = valid                                            # (and some valid-valid blocks)
+            else:
+                make = refused[b % len(refused)] if (t < grid) == first_refused else valid
+        else:
+            make = valid if rng.random() < 0.8 else refused[int(rng.integers(0, len(refused)))]
+        rows[t], want[t] = make()
+    return rows, want
+
+
+def test_chisq_block_reuse_and_status_mix():
+    """5000 tests on the 4096-block grid: blocks 0..903 run a second test (t + 4096), with a
+    refused test before a valid one and the other way round. n = 8, N = 300, cards 1..4 with a
+    single-level variable used as x, as y and in S, max_cells = 256. Refused: well-formed rows
+    whose strata product alone exceeds max_cells (status 4), rows whose full table does (4),
+    malformed rows (3), rows through a variable holding an out-of-range sample (3). With cards
+    <= 4 a strata product needs five variables to pass 256, so those rows have d = 5 (stride 8);
+    every other row has d <= 3. Valid rows: statistic and df bitwise the oracle's."""
+    import torch
+    from rcaeval_amd.engine import get_engine
+    rng = np.random.default_rng(5000)
+    n, N, count, stride, max_cells = 8, 300, 5000, 8, 256
+    card = _MIX_CARD
+    codes = np.stack([rng.integers(0, c, N) for c in card], 1)
+    codes[:, 2] = (codes[:, 0] + rng.integers(0, 2, N)) % card[2]
+    codes[17, _MIX_BAD_VAR] = card[_MIX_BAD_VAR]                          # outside [0, card)
+    rows, want = _mix_rows(rng, count, stride, max_cells)
+    assert {int(v) for v in want} == {0, 3, 4}
+    valid = np.flatnonzero(want == 0)
+    used = rows[valid]
+    assert (used[:, 0] == 1).any() and (used[:, 1] == 1).any() and (used[:, 3:] == 1).any()   # card 1 as x, y, in S
+    t2 = np.arange(count - 4096)
+    assert ((want[t2] != 0) & (want[t2 + 4096] == 0)).sum() > 100
+    assert ((want[t2] == 0) & (want[t2 + 4096] != 0)).sum() > 100
+    over = rows[(want == 4) & (rows[:, 2] == 5)]
+    assert len(over) > 50 and (np.prod(card[over[:, 3:8]], axis=1) > max_cells).all()
+    eng = get_engine(0)
+    data = torch.from_numpy(np.ascontiguousarray(codes.T.astype(np.int32))).to(eng.device)
+    cd = torch.from_numpy(card.astype(np.int32)).to(eng.device)
+    stat, df, st = eng.chisq_batch(data, cd, N, n, rows, False, max_cells)
+    np.testing.assert_array_equal(st, want)
+    assert np.isnan(stat[want != 0]).all() and (df[want != 0] == 0).all()
+    memo = {}
+    for t in valid:
+        a, b, d = (int(v) for v in rows[t, :3])
+        S = [int(v) for v in rows[t, 3:3 + d]]
+        key = (a, b, tuple(S))
+        if key not in memo:
+            memo[key] = och.chisq_or_gsq_stat(codes[:, S + [a, b]].T, card[S + [a, b]], False)
+        assert (stat[t], df[t]) == memo[key], (t, key, stat[t], df[t], memo[key])
+
+
+@pytest.mark.parametrize("N", [1, 255, 257])
+@pytest.mark.parametrize("gsq", [False, True])
+def test_chisq_degenerate_shapes(N, gsq):
+    """stride == 3 (no room for a conditioning set: d = 0 rows only) and sample counts of one, one
+    below and one above the 256-thread block."""
+    import torch
+    from rcaeval_amd.engine import get_engine
+    rng = np.random.default_rng(N)
+    card = np.array([2, 3, 4, 1, 3, 4])
+    n = len(card)
+    codes = np.stack([rng.integers(0, c, N) for c in card], 1)
+    codes[:, 1] = (codes[:, 0] + rng.integers(0, 2, N)) % card[1]
+    codes[:, 5] = (codes[:, 2] + (rng.random(N) < 0.2)) % card[5]
+    rows = np.array([[a, b, 0] for a in range(n) for b in range(a + 1, n)], np.int32)
+    assert rows.shape[1] == 3
+    eng = get_engine(0)
+    data = torch.from_numpy(np.ascontiguousarray(codes.T.astype(np.int32))).to(eng.device)
+    cd = torch.from_numpy(card.astype(np.int32)).to(eng.device)
+    stat, df, st = eng.chisq_batch(data, cd, N, n, rows, gsq, 16)
+    assert (st == 0).all()
+    for r, (a, b, _) in enumerate(rows.tolist()):
+        want, wdf = och.chisq_or_gsq_stat(codes[:, [a, b]].T, card[[a, b]], gsq)
+        assert df[r] == wdf
+        if gsq:
+            assert abs(stat[r] - want) <= 1e-13 * abs(want), (r, stat[r], want)
+        else:
             assert stat[r] == want, (r, stat[r], want)
 
 

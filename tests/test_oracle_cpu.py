@@ -109,6 +109,22 @@ def test_pagerank_kernel_algorithm_matches_golden():
         np.testing.assert_array_equal(kernel_pagerank(A.tolist()), s)
 
 
+def test_pagerank_kernel_algorithm_signed_weights():
+    """Signed weights: a row of non-zero entries whose signed sum is exactly 0 is dangling in the
+    reference (out_deg = (A @ 1).astype(bool)) while normalize still divides it by sum |a|. The
+    replica of k_pagerank equals the oracle bitwise; the same replica with the dangling flag
+    taken from sum |a| (the kernel's earlier form) does not."""
+    from scipy import sparse
+    from tests_support import kernel_pagerank, signed_pagerank_matrix
+    A, cancel, zero = signed_pagerank_matrix(50, 50)
+    assert len(cancel) >= 3 and len(zero) >= 3
+    assert (np.count_nonzero(A[cancel], axis=1) >= 2).all() and (sparse.csr_matrix(A).dot(np.ones(50))[cancel] == 0).all()
+    assert not A[zero].any()
+    ref = opr.pagerank(A)
+    np.testing.assert_array_equal(kernel_pagerank(A.tolist()), ref)
+    assert not np.array_equal(kernel_pagerank(A.tolist(), dangling_from_abs=True), ref)
+
+
 def test_pcg64_replica_matches_numpy():
     st = np.random.default_rng(0).bit_generator.state["state"]
     mine = orw.pcg64_doubles(st["state"], st["inc"], 50)

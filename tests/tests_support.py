@@ -27,18 +27,21 @@ def pairwise_sum(a):
     return pairwise_sum(a[:n2]) + pairwise_sum(a[n2:])
 
 
-def kernel_pagerank(A, d=0.85, n_iter=10, tol=1e-6):
-    """Statement-by-statement replica of k_pagerank (rcaeval_amd/csrc/pagerank.hip)."""
+def kernel_pagerank(A, d=0.85, n_iter=10, tol=1e-6, dangling_from_abs=False):
+    """Statement-by-statement replica of k_pagerank (rcaeval_amd/csrc/pagerank.hip).
+    ``dangling_from_abs`` restates the kernel as it was before the dangling flag came from the
+    signed row sum (a row whose entries cancel then counted as not dangling)."""
     import numpy as np
     m = len(A)
     inv = [0.0] * m
     b = [0.0] * m
     for j in range(m):
-        rs = 0.0
+        rs = sg = 0.0
         for k in range(m):
             rs += abs(A[j][k])
+            sg += A[j][k]
         inv[j] = 1.0 / rs if rs != 0 else 0.0
-        b[j] = (1.0 - d * (1.0 if rs != 0 else 0.0)) * (1.0 / m)
+        b[j] = (1.0 - d * (1.0 if (rs if dangling_from_abs else sg) != 0 else 0.0)) * (1.0 / m)
     cols = [[(j, d * (inv[j] * A[j][i])) for j in range(m) if A[j][i] != 0] for i in range(m)]
     s = list(b)
     for _ in range(n_iter):
@@ -57,6 +60,34 @@ def kernel_pagerank(A, d=0.85, n_iter=10, tol=1e-6):
         s = s2
     fin = pairwise_sum(s)
     return np.array([v / fin for v in s])
+
+
+def signed_pagerank_matrix(m, seed):
+    """Sparse signed weights for PageRank: rows of all zeros; rows of +w, -w pairs in adjacent
+    non-zero positions (non-zero entries whose signed sum, taken in column order, is exactly 0:
+    dangling in the reference's out_deg = (A @ 1) != 0, yet normalised by sum |a|); rows holding
+    +w1 +w2 +w3 -w1 -w2 -w3, whose sequential sum cancels only up to rounding, so the flag depends
+    on the order of summation; and ordinary signed rows.
+    Returns (A, exactly cancelling rows, zero rows)."""
+    rng = np.random.default_rng(seed)
+    A = (rng.random((m, m)) < min(1.0, 6.0 / m)) * rng.uniform(-1.0, 1.0, (m, m))
+    rows = rng.permutation(m)
+    k = max(3, m // 10)
+    cancel, zero, near = np.sort(rows[:k]), np.sort(rows[k:2 * k]), rows[2 * k:3 * k]
+    A[zero] = 0.0
+    for j in cancel:
+        A[j] = 0.0
+        cols = np.sort(rng.choice(m, size=2 * int(rng.integers(1, 4)), replace=False))
+        w = rng.uniform(0.1, 1.0, len(cols) // 2)
+        A[j, cols[0::2]] = w
+        A[j, cols[1::2]] = -w
+    for j in near:
+        A[j] = 0.0
+        cols = np.sort(rng.choice(m, size=6, replace=False))
+        w = rng.uniform(0.1, 1.0, 3)
+        A[j, cols[:3]] = w
+        A[j, cols[3:]] = -w
+    return A, cancel, zero
 
 
 def unions_from_oracle(ref, n):

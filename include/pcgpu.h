@@ -140,7 +140,7 @@ int pcg_set_record_sample(pcg_handle *h, int64_t modulus, int64_t residue);
                                      (0 = the default split)                                     */
 #define PCG_TUNE_SCREEN_MASK 5    /* depths (bit 1 << d, d = 2..4) of the fp32-screened sweep;
                                      -1 = pcg_set_screen_precision's choice (0x18)               */
-#define PCG_TUNE_NODE_BLOCKS 6    /* depths (bit 1 << d) that stage compact node blocks (0x10)    */
+#define PCG_TUNE_NODE_BLOCKS 6    /* depths (bit 1 << d) that stage compact node blocks (0x18)    */
 #define PCG_TUNE_EXPORT_INLINE 7  /* graphs of at most this many CSR entries export their sepset
                                      rows on the handle's stream (16384)                          */
 #define PCG_TUNE_NB 8             /* narrow-class blocks per depth and rank (0 = per-depth default) */
@@ -293,6 +293,12 @@ int pcg_level_begin(pcg_handle *h, int depth, int64_t *total_chunks, int32_t *ma
                     uint8_t **rm_dev);
 int pcg_level_run(pcg_handle *h, int64_t chunk_lo, int64_t chunk_hi);
 int pcg_level_end(pcg_handle *h, pcg_stats *stats);
+/* Depths 2..4 of a one-GPU run may have their nodes' fp32 images built right behind the previous
+ * depth's barrier, laid out by a scan on the device; the level's begin then checks the device's
+ * total size against the host's own decomposition (PCG_ERR_INVALID if they differ). Both totals
+ * (in doubles) of `depth` in the handle's last skeleton run; -1, -1 when that depth's images were
+ * not built that way (sharded runs, sub-ranges, no images at that depth, depth not reached).     */
+int pcg_level_image_totals(pcg_handle *h, int depth, int64_t *host_doubles, int64_t *device_doubles);
 /* Work weight of each chunk prefix (host out, total_chunks+1 int64) for load balance.  */
 int pcg_level_chunk_work(pcg_handle *h, int64_t *prefix_host, int64_t capacity);
 /* The contiguous work-balanced chunk range [lo, hi) of `rank` (the same cut as

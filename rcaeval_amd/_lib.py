@@ -143,6 +143,7 @@ SIGNATURES = [
     ("pcg_level_begin", I32, [P, ctypes.c_int, ctypes.POINTER(I64), ctypes.POINTER(I32), ctypes.POINTER(P)]),
     ("pcg_level_run", I32, [P, I64, I64]),
     ("pcg_level_end", I32, [P, ctypes.POINTER(PcgStats)]),
+    ("pcg_level_image_totals", I32, [P, ctypes.c_int, ctypes.POINTER(I64), ctypes.POINTER(I64)]),
     ("pcg_level_chunk_work", I32, [P, P, I64]),
     ("pcg_level_split", I32, [P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(I64), ctypes.POINTER(I64)]),
     ("pcg_set_removal_buffer", I32, [P, P, I64]),

@@ -89,7 +89,7 @@ const TuneSpec kTune[PCG_TUNE_COUNT] = {
     {"PCG_LDS_SPILL_MIN", 10000000, 0, INT64_MAX},
     {"PCG_WAVE_LO", 0, 0, PCG_MAX_LEVEL_DEPTH + 1},
     {"PCG_SCREEN_MASK", -1, -1, 0x1c},
-    {"PCG_NODE_BLOCKS", 0x10, 0, 0x1c},
+    {"PCG_NODE_BLOCKS", 0x18, 0, 0x1c},
     {"PCG_EXPORT_INLINE", 16384, 0, INT64_MAX},
     {"PCG_NB", 0, 0, 1 << 24},
     {"PCG_NBW", 512, 1, 1 << 24},
@@ -172,7 +172,7 @@ extern "C" int pcg_destroy(pcg_handle *h) {
     DevBuf *bufs[] = {&h->adj, &h->deg, &h->off2[0], &h->off2[1], &h->nbr2[0], &h->nbr2[1], &h->rm, &h->ug2[0],
                       &h->ug2[1], &h->exp_ctr, &h->cpre, &h->binom, &h->ctr,
                       &h->deferred, &h->screenq, &h->records, &h->nearbuf, &h->exportbuf, &h->export_xy, &h->diag,
-                      &h->colmean, &h->pr_scratch, &h->batch_scratch, &h->chisq_scratch, &h->cblk, &h->lmk,
+                      &h->colmean, &h->pr_scratch, &h->batch_scratch, &h->chisq_scratch, &h->cblk, &h->lmk, &h->ibo,
                       &h->k1_digits, &h->small_sum, &h->batch_up, &h->batch_sum, &h->batch_near,
                       &h->granger_scratch, &h->granger_work, &h->lingam_w, &h->lingam_z, &h->lingam_d,
                       &h->lingam_small};

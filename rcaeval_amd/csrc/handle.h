@@ -43,6 +43,7 @@ struct LevelSummary {
     DevCounters ctr;
     uint8_t status[8];
     int32_t ug_clean;              // k_summary_fill cleared every union row of the new graph
+    long long img_total;           // doubles of the next depth's node images as the device scanned them (-1: not asked)
     unsigned long long stamp;      // device wall-clock ticks when the summary was written
     unsigned long long seq;        // written last, after a system-scope fence
 };
@@ -152,6 +153,19 @@ struct pcg_handle {
     bool l1z_pre = false;            // depth 1's per-edge C values (k_edge_c) enqueued by pcg_level_begin
     bool nimg = false;               // ... as fp32 LDS images of k_level_lds_f (k_node_blocks_t)
     DevBuf cblk, lmk;                // k_node_blocks: per-node compact correlation blocks, local masks
+    // Node images built behind the previous depth's summary (level_end_enqueue), while the host is
+    // still waiting for it: k_summary_fill scans the image offsets into ibo (n + 1 doubles offsets)
+    // and k_node_blocks_t takes the narrow class from the degree bounds [pre_lo, pre_hi]
+    DevBuf ibo;
+    bool pre_ok = false;             // the current depth may build the next depth's images (level_begin_impl)
+    int pre_lo = 0, pre_hi = -1;     // ... whose narrow class with work is deg in [pre_lo, pre_hi]
+    int64_t pre_bound = 0;           // ... and take at most this many doubles (from the current degrees)
+    int pre_depth = -1;              // the depth whose images were enqueued that way (-1: none)
+    int64_t pre_total = -1;          // the device's image total for that depth (from the summary)
+    bool img_ready = false;          // the current depth's images are those: run_narrow builds none
+    int run_calls = 0;               // pcg_level_run calls at the current depth
+    bool run_whole = false;          // ... a single one, over the whole chunk range
+    int64_t img_host[PCG_MAX_DEPTH + 1] = {}, img_dev[PCG_MAX_DEPTH + 1] = {};   // pcg_level_image_totals
     int64_t bo_off = 0;              // int64 offset of the compact-block offsets in cpre / cpre_pin
     int64_t lpt_off = 0;             // ... of k_level_lds_f's dispatch order (int32 nps, then nord)
     int nlpt = 0;                    // nodes in that order (0: canonical order)

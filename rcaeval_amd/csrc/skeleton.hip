@@ -55,7 +55,9 @@
 #define PCG_F32_KE 32.0         // fp32 screen: E = 2 KE u32 (1 + nu^2) >= KE u32 (1 + nu)^2, 1.75x DESIGN §4.1's 18 u32 (1 + nu)^2
 #endif
 #ifndef PCG_TG_F32
-#define PCG_TG_F32 0x18         // depths whose T-group sweep is fp32-screened (k_level_lds_f) by default
+#define PCG_TG_F32 0x18         // depths whose T-group sweep is fp32-screened (k_level_lds_f) by default (depth 2
+                                // from images, 0x1c with node blocks 0x1c: narrow sweep 168 -> 148 us, the level
+                                // 0.248-0.254 -> 0.254-0.292 ms: its builder does not fit the short hop there)
 #endif
 // T-group kernels (k_level_lds_t, k_level_lds_f): candidates c per lane task, per depth (measured,
 // tools/variant_bench.sh): depth 2 groups of 6 (0.314 -> 0.282 ms vs 8, which had been -28 % vs 4);
@@ -112,7 +114,9 @@
 #ifndef PCG_TGF_LPT
 #define PCG_TGF_LPT 0x10        // depths whose narrow class is dispatched largest degree first (LevelArgs::nord;
                                 // config 5 depth 4: kernel 1.715-1.74 -> 1.69-1.70 ms A/B; depth 3 measured
-                                // 0.68-0.69 -> 0.69-0.72: its largest-degree blocks staged together first)
+                                // 0.68-0.69 -> 0.69-0.72: its largest-degree blocks staged together first;
+                                // again with depth 3 staged from images by DMA: level 0.469-0.482 vs 0.457-0.488 ms,
+                                // no gain, left off)
 #endif
 #ifndef PCG_SCREEN_BUF
 #define PCG_SCREEN_BUF 96       // screen list entries a block buffers in LDS before its one counter atomic
@@ -162,6 +166,14 @@ __host__ __device__ constexpr int tg_of_depth(int d) { return d == 2 ? PCG_TG2 :
 static_assert((PCG_TG2 == 4 || PCG_TG2 == 6 || PCG_TG2 == 8) && (PCG_TG3 == 4 || PCG_TG3 == 6 || PCG_TG3 == 8) &&
                   (PCG_TG4 == 4 || PCG_TG4 == 6 || PCG_TG4 == 8),
               "k_level_lds_t candidate groups of 4, 6 or 8");
+
+// k_level_lds_f's staged region of a node of degree D: M (D rows of DS floats, columns >= D zero),
+// the DS y records (2 mb bytes each) and nxs (DS ints). Narrow (mb = 8): rounded to 1 KB, the unit a
+// wave's LDS-DMA instruction writes (64 lanes x 16 B), so a node image is copied whole
+__host__ __device__ constexpr int tgf_image_bytes(int D, int mb) {
+    return mb == 8 ? (4 * D * ((D + 3) & ~3) + (2 * mb + 4) * ((D + 3) & ~3) + 1023) & ~1023
+                   : (4 * D * ((D + 3) & ~3) + (2 * mb + 4) * ((D + 3) & ~3) + 15) & ~15;
+}
 
 struct LevelArgs {
     const double *C;
@@ -593,7 +605,9 @@ __global__ __launch_bounds__(256) void k_level_close(uint8_t *rm, uint64_t *adj,
 // one wave per node x builds its ascending neighbour list from the adjacency row at offset
 // sum(deg[0..x)) (each wave sums the prefix itself, so no grid-wide scan is waited for) and, with
 // ug, clears the node's union rows when they lie inside the buffer's ug_rows rows (the last block
-// reports whether all of them did, so the next depth skips its memset). The last block: the CSR offsets (exclusive scan of deg), the
+// reports whether all of them did, so the next depth skips its memset). The last block: the CSR offsets (exclusive scan of deg),
+// on request the next depth's node-image offsets (a second scan, for the builder launched right behind
+// this kernel: level_end_enqueue), the
 // degrees, level counters and merged status bytes written into host-mapped memory, then — after
 // a system-scope fence — the sequence number the host spins on (the host then enqueues work that
 // the stream orders after the whole grid). Counters and status bytes are cleared once copied.
@@ -638,43 +652,105 @@ __device__ __forceinline__ void summary_nodes(const int32_t *deg, int n, int W, 
 
 // the summary part (one block): CSR offsets, degrees, counters, status bytes -> host-mapped
 // memory, then the sequence number
-__device__ __forceinline__ void summary_block(const int32_t *deg, int n, int32_t *off, const uint64_t *ug,
-                                              int64_t ug_rows, DevCounters *ctr, uint8_t *status, LevelSummary *out,
-                                              int32_t *out_deg, unsigned long long seq, int nfill, int32_t *part) {
-    const int tid = threadIdx.x;
-    const int per = (n + 255) / 256;
-    const int lo = min(n, tid * per), hi = min(n, lo + per);
-    int32_t sum = 0;
-    for (int i = lo; i < hi; ++i) {
-        const int32_t v = deg[i];
-        out_deg[i] = v;
-        sum += v;
-    }
-    part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {        // inclusive Hillis-Steele scan of the chunk sums
-        const int32_t v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int32_t acc = tid ? part[tid - 1] : 0;
-    for (int i = lo; i < hi; ++i) { off[i] = acc; acc += deg[i]; }
-    if (tid == 255) off[n] = part[255];
-    if (tid == 0) {
+__device__ __forceinline__ void summary_block(const int32_t *__restrict__ deg, int n, int32_t *__restrict__ off,
+                                              const uint64_t *ug, int64_t ug_rows, DevCounters *ctr, uint8_t *status,
+                                              LevelSummary *out, int32_t *__restrict__ out_deg, unsigned long long seq,
+                                              int nfill, int32_t *part, int64_t *__restrict__ ibo, int img_lo, int img_hi) {
+    // Two exclusive scans over the nodes, lane-coalesced: the CSR offsets (deg) and, with ibo, the
+    // next depth's node-image offsets in doubles (a node of degree D in [img_lo, img_hi], the next
+    // depth's narrow class as the host will decide it, takes tgf_image_bytes(D, 8); every other
+    // node nothing; the host only asks when the total fits an int). A wave takes a contiguous
+    // segment of the nodes in tiles of U x 64 whose U loads are all issued before the first is used
+    // (the block is latency-bound: a dependent round trip per 64 nodes was most of its time): one
+    // pass for the segment sums (and the degrees' copy to the host), one block barrier, then a
+    // shuffle scan per 64 nodes with the carry in a register.
+    constexpr int U = 8;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    // the level's counters and status bytes, a lane each: one round trip for all of them, and the
+    // stores to the host are on their way while the scans run
+    if (wv == 3) {
         volatile unsigned long long *cw = reinterpret_cast<volatile unsigned long long *>(ctr);
         unsigned long long *ow = reinterpret_cast<unsigned long long *>(&out->ctr);
         constexpr int NW = (int)(sizeof(DevCounters) / sizeof(unsigned long long));
-        const int near_w = (int)(offsetof(DevCounters, near_alpha) / sizeof(unsigned long long));
-        for (int k = 0; k < NW; ++k) {
-            ow[k] = cw[k];
-            if (k != near_w) cw[k] = 0ull;    // the near-alpha list accumulates over the run
+        constexpr int near_w = (int)(offsetof(DevCounters, near_alpha) / sizeof(unsigned long long));
+        static_assert(NW <= 64 && PCG_RM_STATUS <= 64, "a lane per counter word / status byte");
+        if (lane < NW) {
+            ow[lane] = cw[lane];
+            if (lane != near_w) cw[lane] = 0ull;    // the near-alpha list accumulates over the run
         }
         const volatile uint8_t *sv = status;
-        for (int k = 0; k < 8; ++k) out->status[k] = status ? sv[k] : 0;
-        out->ug_clean = ug != nullptr && nfill > 0 && (int64_t)part[255] <= ug_rows;
-        if (status)
-            for (int k = 0; k < PCG_RM_STATUS; ++k) status[k] = 0;
+        if (lane < 8) out->status[lane] = status ? sv[lane] : 0;
+        if (status && lane < PCG_RM_STATUS) status[lane] = 0;   // (a lane clears the byte it has just read)
+    }
+    const int seg = ((n + 255) / 256) * 64;
+    const int lo = min(n, wv * seg), hi = min(n, lo + seg);
+    auto img_of = [&](int D) { return (ibo && D >= img_lo && D <= img_hi) ? tgf_image_bytes(D, 8) / 8 : 0; };
+    int32_t sd = 0, si = 0;
+    for (int b = lo; b < hi; b += 64 * U) {
+        int32_t v[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const int i = b + 64 * k + lane;
+            v[k] = i < hi ? deg[i] : -1;
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const int i = b + 64 * k + lane;
+            if (v[k] >= 0) {
+                out_deg[i] = v[k];
+                sd += v[k];
+                si += img_of(v[k]);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sd += __shfl_xor(sd, o);
+        si += __shfl_xor(si, o);
+    }
+    if (lane == 0) {
+        part[wv] = sd;
+        part[4 + wv] = si;
+    }
+    __syncthreads();
+    int32_t accd = 0, acci = 0, totd = 0, toti = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k < wv) { accd += part[k]; acci += part[4 + k]; }
+        totd += part[k];
+        toti += part[4 + k];
+    }
+    for (int b = lo; b < hi; b += 64 * U) {
+        int32_t v[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const int i = b + 64 * k + lane;
+            v[k] = i < hi ? deg[i] : -1;
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            if (b + 64 * k >= hi) break;            // wave-uniform
+            const int i = b + 64 * k + lane;
+            const int32_t d = max(v[k], 0), m = v[k] >= 0 ? img_of(v[k]) : 0;
+            int32_t iv = d, im = m;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int32_t tv = __shfl_up(iv, o), tm = __shfl_up(im, o);
+                if (lane >= o) { iv += tv; im += tm; }
+            }
+            if (v[k] >= 0) {
+                off[i] = accd + iv - d;
+                if (ibo) ibo[i] = (int64_t)(acci + im - m);
+            }
+            accd += __shfl(iv, 63);
+            acci += __shfl(im, 63);
+        }
+    }
+    if (tid == 0) {
+        off[n] = totd;
+        if (ibo) ibo[n] = (int64_t)toti;
+        out->img_total = ibo ? (long long)toti : -1ll;
+        out->ug_clean = ug != nullptr && nfill > 0 && (int64_t)totd <= ug_rows;
         out->stamp = wall_clock64();
     }
     __threadfence_system();
@@ -688,13 +764,14 @@ __device__ __forceinline__ void summary_block(const int32_t *deg, int n, int32_t
 __global__ __launch_bounds__(256) void k_summary_fill(const int32_t *deg, int n, int W, const uint64_t *adj,
                                                       int32_t *off, int32_t *nbr, uint64_t *ug, int64_t ug_rows,
                                                       DevCounters *ctr, uint8_t *status, LevelSummary *out,
-                                                      int32_t *out_deg, unsigned long long seq, int nfill) {
+                                                      int32_t *out_deg, unsigned long long seq, int nfill,
+                                                      int64_t *ibo, int img_lo, int img_hi) {
     if ((int)blockIdx.x < nfill) {
         summary_nodes(deg, n, W, adj, nbr, ug, ug_rows, nfill, blockIdx.x, nfill);
         return;
     }
-    __shared__ int32_t part[256];
-    summary_block(deg, n, off, ug, ug_rows, ctr, status, out, out_deg, seq, nfill, part);
+    __shared__ int32_t part[8];
+    summary_block(deg, n, off, ug, ug_rows, ctr, status, out, out_deg, seq, nfill, part, ibo, img_lo, img_hi);
 }
 
 // The node owning a chunk: the last x < n with cpre[x] <= chunk (the caller checked chunk <
@@ -2465,13 +2542,6 @@ __global__ __launch_bounds__(256, WIDE ? 1 : tg_minblocks(DM)) void k_level_lds_
 // decides it like the fp64 kernels (band -> exact path). Decisions are therefore the fp64
 // kernels' decisions; only where the fp32 sweep is certain does it decide.
 typedef float f2v __attribute__((ext_vector_type(2)));
-// k_level_lds_f's staged region of a node of degree D: M (D rows of DS floats, columns >= D zero),
-// the DS y records (2 mb bytes each) and nxs (DS ints). Narrow (mb = 8): rounded to 1 KB, the unit a
-// wave's LDS-DMA instruction writes (64 lanes x 16 B), so a node image is copied whole
-__host__ __device__ constexpr int tgf_image_bytes(int D, int mb) {
-    return mb == 8 ? (4 * D * ((D + 3) & ~3) + (2 * mb + 4) * ((D + 3) & ~3) + 1023) & ~1023
-                   : (4 * D * ((D + 3) & ~3) + (2 * mb + 4) * ((D + 3) & ~3) + 15) & ~15;
-}
 struct alignas(16) YRecN {       // k_level_lds_f (narrow): a y's {A~_yy, A~_xy} and local adjacency mask
     f2v md;
     unsigned long long lm;
@@ -3347,8 +3417,9 @@ __global__ __launch_bounds__(256) void k_screen(LevelArgs a) {
 // the per-node compact blocks of the nodes with a chunk in [s_lo, s_hi): C[adj(x) + x, adj(x) + x]
 // (row-major, stride D + 1, x last; each C entry read once, in C's own orientation) and the
 // local adjacency masks (bit k of row t: nbr t and nbr k adjacent). Staged at the depths of
-// PCG_TUNE_NODE_BLOCKS (depth 4: kernel 2.13-2.16 -> 2.08 ms, FETCH 1.8 -> 0.18 GB; depth 3 measured
-// no gain); this gathering form serves the graphs whose C row does not fit k_node_blocks_t's LDS
+// PCG_TUNE_NODE_BLOCKS (depth 4: kernel 2.13-2.16 -> 2.08 ms, FETCH 1.8 -> 0.18 GB; depth 3 gained
+// nothing while its builder sat between the prefix copy and the sweep, and 0.483-0.495 -> 0.457-0.467 ms
+// per level once the images were built behind the previous summary: DESIGN §9); this gathering form serves the graphs whose C row does not fit k_node_blocks_t's LDS
 __global__ __launch_bounds__(256) void k_node_blocks(LevelArgs a, int64_t s_lo, int64_t s_hi) {
     const int x = blockIdx.x;
     if (a.cpre[x + 1] <= s_lo || a.cpre[x] >= s_hi || a.cpre[x + 1] == a.cpre[x]) return;
@@ -3383,7 +3454,13 @@ __global__ __launch_bounds__(256) void k_node_blocks(LevelArgs a, int64_t s_lo, 
 // row iy of M = fp32(C[y][ids_x[k]]) (zero-padded to DS), y's record {fp32(C[y][y]), ., local mask},
 // and from x's own row (y = x) every record's fp32(C[x][ids_x[k]]) and the id list — the values the
 // kernel's own staging computes, so the sweep's results are unchanged
-__global__ __launch_bounds__(256) void k_node_blocks_t(LevelArgs a, int64_t s_lo, int64_t s_hi, int maxdeg) {
+// DEV: launched right behind the previous depth's k_summary_fill, before the host has decomposed the
+// level: a node has a block when its degree lies in [dlo, dhi] (the narrow class with work, the bounds
+// the host's rule gives) and its offset is the one k_summary_fill scanned (ibo); neither cpre nor
+// bo exists yet. maxdeg may be any upper bound of the degrees (it only sizes the descriptors).
+template <bool DEV>
+__global__ __launch_bounds__(256) void k_node_blocks_t(LevelArgs a, int64_t s_lo, int64_t s_hi, int maxdeg,
+                                                       const int64_t *ibo, int dlo, int dhi) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double *row = reinterpret_cast<double *>(smem);
     uint64_t *arow = reinterpret_cast<uint64_t *>(row + a.n);
@@ -3397,11 +3474,14 @@ __global__ __launch_bounds__(256) void k_node_blocks_t(LevelArgs a, int64_t s_lo
     bool any = false;
     for (int t = threadIdx.x; t <= Dy; t += blockDim.x) {
         const int x = t < Dy ? ny[t] : y;
-        const bool hb = !(a.cpre[x + 1] <= s_lo || a.cpre[x] >= s_hi || a.cpre[x + 1] == a.cpre[x]);
+        const int Dx = a.deg[x];
+        bool hb;
+        if constexpr (DEV) hb = Dx >= dlo && Dx <= dhi;
+        else hb = !(a.cpre[x + 1] <= s_lo || a.cpre[x] >= s_hi || a.cpre[x + 1] == a.cpre[x]);
         tx[t] = hb ? x : -1;
-        tD[t] = a.deg[x];
+        tD[t] = Dx;
         toff[t] = a.off[x];
-        tbo[t] = hb ? a.bo[x] : 0;
+        tbo[t] = hb ? (DEV ? ibo[x] : a.bo[x]) : 0;
         any = any || hb;
     }
     if (!__syncthreads_or(any)) return;
@@ -4714,7 +4794,8 @@ LevelArgs make_args(pcg_handle *h, int d, int mode_exact_all) {
     a.rec_res = h->rec_res;
     a.spl = h->spl;
     if (h->nblk) {
-        a.bo = (const int64_t *)h->cpre.p + h->bo_off;
+        // (images built behind the previous summary sit at the offsets the device scanned)
+        a.bo = h->img_ready ? (const int64_t *)h->ibo.p : (const int64_t *)h->cpre.p + h->bo_off;
         a.cblk = (double *)h->cblk.p;
         a.lmk = (uint64_t *)h->lmk.p;
         a.img = h->nimg ? 1 : 0;
@@ -4847,8 +4928,8 @@ bool use_l1_pairs(const pcg_handle *h, int d) { return d == 1 && mode_of(h, d) =
 int64_t l1_pair_chunks(int D) { return std::max<int64_t>(1, ((int64_t)D * (D - 1) / 2 + L1_PAIRS_PER_CHUNK - 1) / L1_PAIRS_PER_CHUNK); }
 
 // node class of a degree-D node at depth d: 0 narrow, 1 wide (T-group depths only), 2 large
-int level_class(const pcg_handle *h, int D, int d, bool tg) {
-    if (h->wavek) return D <= std::min(WAVE_MAXD, h->narrow_deg) ? 0 : 2;   // k_level_wave depths
+int level_class(const pcg_handle *h, int D, int d, bool tg, bool wavek) {
+    if (wavek) return D <= std::min(WAVE_MAXD, h->narrow_deg) ? 0 : 2;   // k_level_wave depths
     if (D <= std::min(SMALL_DEG, h->narrow_deg) &&
         (d <= PCG_MAX_DEPTH || (mode_of(h, d) == MODE_DECIDE && d <= lds_deep_max(h))))
         return 0;
@@ -4860,6 +4941,45 @@ int mode_of(const pcg_handle *h, int d) {
     if ((h->flags & PCG_FLAG_EXACT_ALL) || (double)h->N - d - 3 <= 0) return MODE_EXACT;
     if (h->flags & (PCG_FLAG_FULL_P | PCG_FLAG_RECORD)) return MODE_FULLP;
     return MODE_DECIDE;
+}
+
+// fp32-screened depths: PCG_TUNE_SCREEN_MASK, else pcg_set_screen_precision's choice
+int screen_mask_eff(const pcg_handle *h) {
+    const int64_t tm = h->tune[PCG_TUNE_SCREEN_MASK];
+    const int m = tm >= 0 ? (int)tm : (h->screen_mask < 0 ? PCG_TG_F32 : h->screen_mask);
+    return m & 0x1c;   // the error bound (KE = 64) is derived for d = 2..4 only
+}
+// compact node blocks (k_node_blocks) for the narrow class of depth d's fp32-screened sweep
+bool use_node_blocks(const pcg_handle *h, int d, bool tg) {
+    return tg && ((screen_mask_eff(h) >> d) & 1) && ((h->tune[PCG_TUNE_NODE_BLOCKS] >> d) & 1);
+}
+// ... as fp32 LDS images when the transposed builder's row of C fits its LDS (maxd: the largest degree)
+size_t node_images_lds(int64_t n, int W, int maxd) {
+    return 8 * (size_t)n + 8 * (size_t)W + (size_t)(maxd + 1) * (sizeof(int64_t) + 3 * sizeof(int));
+}
+bool use_node_images(int64_t n, int W, int maxd) { return node_images_lds(n, W, maxd) <= 64 * 1024; }
+
+// May depth d1's node images be built right behind depth d1 - 1's summary, from the device's own
+// scan, while the host still waits for that summary? One rank with the handle's own removal flags,
+// a depth the run reaches, fp32-screened with images. The narrow class with work is then deg in
+// [*lo, *hi]: the degrees level_class sends there, read off the rule itself. maxdeg (the degrees now,
+// before depth d1 - 1 removes edges) bounds depth d1's degrees from above.
+bool prebuild_plan(const pcg_handle *h, int d1, int *lo, int *hi) {
+    if (h->world != 1 || h->rm_ext || d1 < 2 || d1 > 4) return false;
+    if (h->run_max_depth >= 0 && d1 > h->run_max_depth) return false;
+    const int mode = mode_of(h, d1);
+    const bool tg = use_tgroup(mode, d1);
+    if (!use_node_blocks(h, d1, tg) || !use_node_images(h->n, h->W, h->maxdeg)) return false;
+    if (use_wave(h, mode, d1, 0.0)) return false;
+    const int top = std::min<int>(h->maxdeg, WIDE_DEG + 1);
+    int l = d1 + 1, u = d1;
+    while (u + 1 <= top && level_class(h, u + 1, d1, tg, false) == 0) ++u;
+    for (int D = u + 1; D <= top; ++D)
+        if (level_class(h, D, d1, tg, false) == 0) return false;   // (not an interval: the host path)
+    if (u < l) return false;
+    *lo = l;
+    *hi = u;
+    return true;
 }
 
 // the summary slot of sequence number seq (a ring of two)
@@ -4923,7 +5043,8 @@ int graph_launch(pcg_handle *h) {
     hipLaunchKernelGGL(k_summary_fill, dim3((unsigned)(nfill + 1)), dim3(256), 0, h->stream,
                        (const int32_t *)h->deg.p, n, W, (const uint64_t *)h->adj.p, (int32_t *)h->off2[t].p,
                        (int32_t *)h->nbr2[t].p, ug, ug_rows, (DevCounters *)h->ctr.p, status, ds,
-                       reinterpret_cast<int32_t *>(ds + 1), seq, nfill);
+                       reinterpret_cast<int32_t *>(ds + 1), seq, nfill,
+                       h->pre_depth >= 0 ? (int64_t *)h->ibo.p : (int64_t *)nullptr, h->pre_lo, h->pre_hi);
     h->cb = t;
     PCG_HIP(h, hipGetLastError());
     return PCG_OK;
@@ -5021,6 +5142,10 @@ extern "C" int pcg_skeleton_init(pcg_handle *h, const double *C, int64_t n, int6
     h->W = (int)((n + 63) / 64);
     h->depth = -1;
     h->deg_levels.clear();
+    h->pre_ok = h->img_ready = false;
+    h->pre_depth = -1;
+    h->pre_total = -1;
+    for (int k = 0; k <= PCG_MAX_DEPTH; ++k) h->img_host[k] = h->img_dev[k] = -1;
     if (h->xs) PCG_HIP(h, hipStreamSynchronize(h->xs));   // a previous run's exports are done
     h->xpending[0] = h->xpending[1] = false;
     h->xany = false;
@@ -5106,6 +5231,13 @@ int l1z_edges(pcg_handle *h) {
     return PCG_OK;
 }
 
+// the host's image total of a depth against the one the device scanned for the builder
+int image_totals_check(pcg_handle *h, int depth, int64_t host_total, int64_t dev_total) {
+    if (host_total == dev_total) return PCG_OK;
+    return pcg_fail(h, PCG_ERR_INVALID, "depth %d: node images laid out on the device take %lld doubles, the host's %lld",
+                    depth, (long long)dev_total, (long long)host_total);
+}
+
 int level_begin_impl(pcg_handle *h, int depth, int64_t *total_chunks) {
     if (!h || depth != h->depth + 1) return pcg_fail(h, PCG_ERR_INVALID, "pcg_level_begin: depth order");
     // reference loop condition: while max_degree() - 1 > depth_prev
@@ -5118,6 +5250,25 @@ int level_begin_impl(pcg_handle *h, int depth, int64_t *total_chunks) {
                         PCG_MAX_LEVEL_DEPTH);
     h->depth = depth;
     const int n = (int)h->n;
+    h->run_calls = 0;
+    h->run_whole = false;
+    // The next depth's images may be built behind this depth's summary (level_end_enqueue): their
+    // buffers are sized here, before anything of this depth is queued, from this depth's degrees
+    // (degrees only fall and an image only shrinks with its degree, so this bounds them; the nodes
+    // that may yet fall to 64 neighbours count as 64). Nothing is allocated between the summary and
+    // the sweep. When this depth's own images were built that way they already sit in cblk: the
+    // bound they were sized by was the previous depth's, which is no smaller, so cblk stays.
+    h->pre_ok = prebuild_plan(h, depth + 1, &h->pre_lo, &h->pre_hi);
+    if (h->pre_ok) {
+        int64_t b = 0;
+        for (int x = 0; x < n; ++x) b += tgf_image_bytes(std::min<int>(h->deg_h[x], SMALL_DEG), 8) / 8;
+        h->pre_bound = b;
+        if (b > INT32_MAX) h->pre_ok = false;   // (k_summary_fill scans the offsets in 32 bits)
+        else if (h->pre_depth == depth && h->cblk.bytes < sizeof(double) * (size_t)b) h->pre_ok = false;   // (never grow over live images)
+        else if (!pcg_ensure(h, h->cblk, sizeof(double) * (size_t)std::max<int64_t>(b, 1)) ||
+                 !pcg_ensure(h, h->ibo, sizeof(int64_t) * (size_t)(n + 1)))
+            return pcg_fail(h, PCG_ERR_OOM, "node images of depth %d", depth + 1);
+    }
     h->l1z_pre = false;
     // depth 1's per-edge C values run while the host decomposes (enqueued behind the prefix copy
     // instead: depth-1 level 0.165-0.174 vs 0.157-0.163 ms, two A/B passes on one box)
@@ -5139,6 +5290,7 @@ int level_begin_impl(pcg_handle *h, int depth, int64_t *total_chunks) {
     std::vector<int64_t> bo;           // compact-block offsets (doubles, k_node_blocks)
     h->nblk = false;
     h->nimg = false;
+    h->img_ready = false;
     h->work_h.assign(n, 0);
     h->maxdeg_small = 0;
     h->maxdeg_wide = 0;
@@ -5173,15 +5325,11 @@ int level_begin_impl(pcg_handle *h, int depth, int64_t *total_chunks) {
             tests_bound += (double)hist[D] * c * (double)(D - depth);
         }
         h->wavek = use_wave(h, mode_of(h, depth), depth, tests_bound);
-        // fp32-screened depths: PCG_TUNE_SCREEN_MASK, else pcg_set_screen_precision's choice
-        const int64_t tm = h->tune[PCG_TUNE_SCREEN_MASK];
-        h->screen_eff = tm >= 0 ? (int)tm : (h->screen_mask < 0 ? PCG_TG_F32 : h->screen_mask);
-        h->screen_eff &= 0x1c;   // the error bound (KE = 64) is derived for d = 2..4 only
+        h->screen_eff = screen_mask_eff(h);
         // compact node blocks (k_node_blocks) for the narrow class of the fp32-screened sweeps
-        h->nblk = tg && use_screen32(h, depth) && ((h->tune[PCG_TUNE_NODE_BLOCKS] >> depth) & 1);
+        h->nblk = use_node_blocks(h, depth, tg);
         // ... as fp32 LDS images when the transposed builder's row of C fits its LDS
-        h->nimg = h->nblk &&
-                  8 * (size_t)n + 8 * (size_t)h->W + (size_t)(maxd + 1) * (sizeof(int64_t) + 3 * sizeof(int)) <= 64 * 1024;
+        h->nimg = h->nblk && use_node_images(n, h->W, maxd);
         std::vector<uint64_t> ns_of(maxd + 1, 0), units_of(maxd + 1, 0);
         std::vector<int> cls_of(maxd + 1, 2);
         double sum_small = 0.0, sum_wide = 0.0, sum_large = 0.0;
@@ -5191,7 +5339,7 @@ int level_begin_impl(pcg_handle *h, int depth, int64_t *total_chunks) {
             if (hist[D] && ns > ((uint64_t)1 << 46))
                 return pcg_fail(h, PCG_ERR_INVALID, "depth %d work too large (deg %d)", depth, D);
             ns_of[D] = ns;
-            cls_of[D] = level_class(h, D, depth, tg);
+            cls_of[D] = level_class(h, D, depth, tg, h->wavek);
             units_of[D] = cls_of[D] < 2 ? (tg ? tgroup_tasks(h, D, depth) : ns) : ns;
             if (!hist[D]) continue;
             if (cls_of[D] == 0) {
@@ -5244,6 +5392,17 @@ int level_begin_impl(pcg_handle *h, int depth, int64_t *total_chunks) {
             if (h->nblk && c == 0) sb += h->nimg ? tgf_image_bytes(D, 8) / 8 : (int64_t)(D + 1) * (D + 1);
         }
         if (h->nblk) bo[n] = sb;
+        // this depth's images were built behind the previous summary: the device's scan must have
+        // laid out exactly what this decomposition would have (the sweep then reads the device's
+        // offsets); a different total means the two rules have drifted apart
+        if (h->pre_depth == depth && h->nimg) {
+            if (depth <= PCG_MAX_DEPTH) {
+                h->img_host[depth] = sb;
+                h->img_dev[depth] = h->pre_total;
+            }
+            if (int rc = image_totals_check(h, depth, sb, h->pre_total)) return rc;
+            h->img_ready = true;
+        }
         cs[n] = ss;
         cw[n] = sw;
         cl[n] = sl;
@@ -5542,12 +5701,14 @@ void run_narrow(pcg_handle *h, const LevelArgs &a, int mode, int64_t s_lo, int64
             else hipLaunchKernelGGL((k_level_wave<32, MODE_FULLP>), grid, block, ldsw, s, as);
         }
     } else if (h->tgroup && use_screen32(h, d)) {
-        if (h->nblk) {   // compact node blocks: the sweep stages them instead of gathering C
+        if (h->nblk && !h->img_ready) {   // compact node blocks: the sweep stages them instead of gathering C
+            // (img_ready: this depth's images were built behind the previous depth's summary)
             // built transposed, as LDS images (C's rows staged in LDS), when a row fits
             const size_t tl = sizeof(double) * (size_t)h->n + sizeof(uint64_t) * (size_t)h->W +
                               (size_t)(h->maxdeg + 1) * (sizeof(int64_t) + 3 * sizeof(int));
             if (h->nimg)
-                hipLaunchKernelGGL(k_node_blocks_t, dim3((unsigned)h->n), dim3(256), tl, s, as, s_lo, s_hi, (int)h->maxdeg);
+                hipLaunchKernelGGL(k_node_blocks_t<false>, dim3((unsigned)h->n), dim3(256), tl, s, as, s_lo, s_hi,
+                                   (int)h->maxdeg, (const int64_t *)nullptr, 0, 0);
             else
                 hipLaunchKernelGGL(k_node_blocks, dim3((unsigned)h->n), dim3(256), 0, s, as, s_lo, s_hi);
         }
@@ -5700,6 +5861,7 @@ extern "C" int pcg_level_run(pcg_handle *h, int64_t chunk_lo, int64_t chunk_hi) 
         return pcg_fail(h, PCG_ERR_INVALID, "pcg_level_run: chunk range");
     const int d = h->depth;
     const int mode = mode_of(h, d);
+    h->run_whole = ++h->run_calls == 1 && chunk_lo == 0 && chunk_hi == h->total_chunks;
     PCG_HT(h, "run:start");
     LevelArgs a = make_args(h, d, mode == MODE_EXACT);
     a.chunk_lo = chunk_lo;
@@ -5743,8 +5905,35 @@ int level_end_enqueue(pcg_handle *h, unsigned long long *seq) {
     PCG_HT(h, "end:tail-launched");
     const int xcb = h->cb;               // depth d's CSR / union buffer set (graph_launch flips cb)
     const int64_t xsum = h->sumdeg;
+    // the next depth's node images go right behind the summary when the device can lay them out
+    // itself (prebuild_plan, decided and sized at this depth's begin) and this rank ran the whole
+    // level: k_summary_fill then also scans their offsets
+    const bool pre = h->pre_ok && h->run_whole && h->ibo.p && h->cblk.bytes >= sizeof(double) * (size_t)h->pre_bound;
+    h->pre_depth = pre ? d + 1 : -1;
+    h->pre_total = -1;
     // degrees + counters + status -> host-mapped summary
     int rc = graph_launch(h);
+    if (!rc && pre) {
+        // Built while the host waits for the summary, decomposes the level and uploads its prefixes
+        // (the device would idle). The builder reads the new graph only: deg, the CSR k_summary_fill
+        // just wrote, C and the adjacency. A depth that then never runs (no node above d + 1
+        // neighbours left) has no degree inside the bounds, and a level without narrow nodes none
+        // either: the launch then writes nothing.
+        LevelArgs b{};
+        b.C = h->C;
+        b.ldc = h->ldc;
+        b.adj = (const uint64_t *)h->adj.p;
+        b.W = W;
+        b.n = n;
+        b.d = d + 1;
+        b.deg = (const int32_t *)h->deg.p;
+        b.off = (const int32_t *)h->off2[h->cb].p;
+        b.nbr = (const int32_t *)h->nbr2[h->cb].p;
+        b.cblk = (double *)h->cblk.p;
+        hipLaunchKernelGGL(k_node_blocks_t<true>, dim3((unsigned)n), dim3(256), node_images_lds(n, W, h->maxdeg), h->stream,
+                           b, (int64_t)0, (int64_t)0, (int)h->maxdeg, (const int64_t *)h->ibo.p, h->pre_lo, h->pre_hi);
+        PCG_HIP(h, hipGetLastError());
+    }
     // graphs whose CSR holds at most PCG_TUNE_EXPORT_INLINE entries export on the handle's stream
     // the last depth of a max_depth-bounded run has no next depth to overlap its export with: it
     // runs right behind the barrier on the handle's stream (no cross-stream hop before the sync)
@@ -5789,6 +5978,7 @@ int level_end_finish(pcg_handle *h, int d, unsigned long long seq, pcg_stats *st
     PCG_HT(h, "end:summary-seen");
     const LevelSummary *sm = sum_slot(h, seq);
     const DevCounters c = sm->ctr;
+    if (h->pre_depth == d + 1) h->pre_total = (int64_t)sm->img_total;
     if (h->stamps) {
         // depth d's boundaries: the summary before it (init's at depth 0, still in the other slot of
         // the ring, which holds seq - 1 until the next launch) and this one
@@ -5937,6 +6127,14 @@ extern "C" int pcg_level_end(pcg_handle *h, pcg_stats *stats) {
     int rc = level_end_enqueue(h, &seq);
     if (rc) return rc;
     return level_end_finish(h, h->depth, seq, stats);
+}
+
+extern "C" int pcg_level_image_totals(pcg_handle *h, int depth, int64_t *host_doubles, int64_t *device_doubles) {
+    if (!h || depth < 0 || depth > PCG_MAX_DEPTH || !host_doubles || !device_doubles)
+        return pcg_fail(h, PCG_ERR_INVALID, "pcg_level_image_totals: depth %d", depth);
+    *host_doubles = h->img_host[depth];
+    *device_doubles = h->img_dev[depth];
+    return PCG_OK;
 }
 
 // the level loop's tail: the exports still on the export stream joined into the
@@ -6152,6 +6350,7 @@ int skeleton_small(pcg_handle *h, const double *C, int64_t n, int64_t ldc, int64
     h->W = 1;
     h->depth = -1;
     h->deg_levels.clear();
+    for (int k = 0; k <= PCG_MAX_DEPTH; ++k) h->img_host[k] = h->img_dev[k] = -1;
     if (h->xs) PCG_HIP(h, hipStreamSynchronize(h->xs));
     h->xpending[0] = h->xpending[1] = false;
     h->xany = false;
@@ -6318,6 +6517,7 @@ void batch_reset_run_state(pcg_handle *h) {
     h->W = 1;
     h->depth = -1;
     h->deg_levels.clear();
+    for (int k = 0; k <= PCG_MAX_DEPTH; ++k) h->img_host[k] = h->img_dev[k] = -1;
     h->xpending[0] = h->xpending[1] = false;
     h->xany = false;
     h->xinl = false;

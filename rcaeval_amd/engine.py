@@ -140,6 +140,15 @@ class Engine:
             for k, v in old.items():
                 self.set_tuning(k, v)
 
+    def image_totals(self, depth: int) -> tuple:
+        """(host, device) size in doubles of ``depth``'s node images in the last level-loop run, when
+        they were built behind the previous depth's barrier from the device's own scan; (-1, -1)
+        when they were not (pcg_level_image_totals)."""
+        hd, dd = ctypes.c_int64(), ctypes.c_int64()
+        check(self.h, self.lib.pcg_level_image_totals(self.h, int(depth), ctypes.byref(hd), ctypes.byref(dd)),
+              "pcg_level_image_totals")
+        return hd.value, dd.value
+
     def k1_plan_signature(self, n: int, N: int) -> int:
         v = ctypes.c_int64()
         check(self.h, self.lib.pcg_k1_plan_signature(self.h, int(n), int(N), ctypes.byref(v)), "pcg_k1_plan_signature")

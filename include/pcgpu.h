@@ -535,6 +535,66 @@ int pcg_lingam_pair_scores(pcg_handle *h, const double *X, int64_t T, int64_t m,
 int pcg_direct_lingam_order(pcg_handle *h, const double *X, int64_t T, int64_t n, int64_t ldx, int32_t *order,
                             double *scores);
 
+/* ---- PCMCI lagged causal graphs (pcmci, microcause) -----------------------------------
+ * Replaces tigramite 4.2.2.1 `PCMCI(dataframe, ParCorr(significance='analytic')).run_pcmci(tau_max,
+ * pc_alpha)` [U] behind RCAEval/graph_construction/pcmci.py:71-103 and
+ * RCAEval/e2e/microcause.py:2298-2305. Node (i, -l) is column i delayed by l, stored as the
+ * expanded column id i * (2 tau_max + 1) + l. Every test uses the rows t = 2 tau_max .. T-1
+ * (cut_off='2xtau_max'), T_eff = T - 2 tau_max of them, so every ParCorr value is a partial
+ * correlation inside the correlation matrix R of the T_eff x n (2 tau_max + 1) lag-expanded data,
+ * which pcg_pcmci_parents computes with pcg_corr's kernels and keeps in the handle.
+ *
+ * Limits (pcg_pcmci_limits; anything else is PCG_ERR_INVALID before anything is read): tau_max in
+ * 1..16, n >= 1, n (2 tau_max + 1) <= 8192, n tau_max <= 2048 (the candidate list of a target
+ * lives in LDS), |Z| <= 62 per test ({Z, x, y} is factorised in 32 KB of LDS), ncrit >= 63,
+ * pcap >= 1, and n * T_eff * 512 bytes of exact-path workspace <= 1 GiB. T_eff < 3 (no degree of
+ * freedom at depth 0) is PCG_ERR_DOMAIN. The handle keeps E (T_eff x W doubles, W = n (2 tau_max +
+ * 1)), R (W x W) and that workspace. Both calls are synchronous on return.
+ *
+ * Fast path: Cholesky of the unit-diagonal R[Z, Z] with x and y carried along. A test keeps its
+ * result only if every pivot, and the variances of x and y given Z, are >= tau and the regression
+ * coefficients g of x and of y on Z have (1 + |g|_1)^2 <= beta_c; anything else is recomputed by the
+ * exact path, Householder QR on the standardized (ddof 0) lagged columns themselves, one block per
+ * test (a column dependent to lstsq's rank tolerance is skipped). Status of a test (pcg_pcmci_mci)
+ * or of a target (pcg_pcmci_parents): 0 ok; 1 a column of the test (of any of the target's tests)
+ * is constant over the window; 2 non-finite input; 3 ok, computed by the exact path
+ * (informational, pcg_pcmci_mci only: pcg_pcmci_parents counts them in exact_items); 4 |Z| above
+ * the cap (for a target: its level loop reached depth 63), or a caller-supplied parent entry that
+ * is no lag 1..tau_max column id (refused, never used as an index). val is NaN under 1, 2, 4.
+ *
+ * pcg_pcmci_parents: PC1 (run_pc_stable, max_conds_dim=None, max_combinations=1) of every target
+ * j, the whole level loop on the device. X: device T x n doubles, row stride ldx. crit: host,
+ * ncrit doubles: crit[d] is the |val| below which a test with |Z| = d has p > pc_alpha (the caller
+ * takes it from the Student-t quantile; 0 where deg_f = T_eff - 2 - d < 1, p being NaN there).
+ * Candidates start as (i, -l), i = 0..n-1, l = 1..tau_max in that order; per depth d each
+ * candidate in list order is tested given the first d entries of the list without itself,
+ * val_min = min(|val|, val_min), removals after the pass, then a stable sort by val_min descending
+ * (ties by previous position); the loop stops when len - 1 < d. Out (device): par_ids, par_val_min
+ * n x pcap (the first min(par_count[j], pcap) parents of target j in final order and their
+ * val_min), par_count n int32, levels n int32 (depths run), tests n int64 (tests made), status n
+ * int32. exact_items: host out, tests of all targets the exact path computed (may be NULL).
+ *
+ * pcg_pcmci_mci: run_mci (tau_min = 0, max_conds_py = max_conds_px = None) on the R the last
+ * pcg_pcmci_parents of the same (T, n, tau_max) left in the handle (anything else is
+ * PCG_ERR_INVALID). par_ids / par_count / pcap: device, laid out as above (from that call or the
+ * caller's own; par_count[j] <= pcap). Item (i, j, tau) at index (i * n + j) * (tau_max + 1) + tau
+ * tests (i, -tau) against (j, 0) given Z = parents[j] without (i, -tau), then each (k, -tau - l)
+ * for (k, -l) in parents[i] not yet in Z. val: device n * n * (tau_max + 1) doubles out; dim: device
+ * int32 out, |Z| (-1 on the untested (i, i, 0), whose val is 0); status: device int32 out.
+ * exact_items: host out, the items the exact path computed (may be NULL). The caller takes
+ * p = 2 t.sf(|val| sqrt(deg_f / (1 - val^2)), deg_f), deg_f = T_eff - 2 - |Z|.                    */
+int pcg_pcmci_parents(pcg_handle *h, const double *X, int64_t T, int64_t n, int64_t ldx, int tau_max,
+                      const double *crit, int32_t ncrit, int32_t *par_ids, double *par_val_min,
+                      int32_t *par_count, int32_t pcap, int32_t *levels, int64_t *tests, int32_t *status,
+                      int64_t *exact_items);
+int pcg_pcmci_mci(pcg_handle *h, int64_t T, int64_t n, int tau_max, const int32_t *par_ids,
+                  const int32_t *par_count, int32_t pcap, double *val, int32_t *dim, int32_t *status,
+                  int64_t *exact_items);
+/* The limits and guards the PCMCI kernels were built with (host-only, any may be NULL); the
+ * documented fast-path error bound of val is 2 beta_c (|Z| + 18) 2^-53 / tau.                     */
+int pcg_pcmci_limits(int32_t *max_tau, int32_t *z_cap, int32_t *max_width, int32_t *max_candidates,
+                     double *tau, double *beta_c);
+
 #ifdef __cplusplus
 }
 #endif

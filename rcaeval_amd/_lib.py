@@ -178,6 +178,11 @@ SIGNATURES = [
     ("pcg_granger_guards", I32, [ctypes.POINTER(D), ctypes.POINTER(D), ctypes.POINTER(D)]),
     ("pcg_lingam_pair_scores", I32, [P, P, I64, I64, I64, P, P]),
     ("pcg_direct_lingam_order", I32, [P, P, I64, I64, I64, P, P]),
+    ("pcg_pcmci_parents", I32, [P, P, I64, I64, I64, ctypes.c_int, P, I32, P, P, P, I32, P, P, P,
+                                ctypes.POINTER(I64)]),
+    ("pcg_pcmci_mci", I32, [P, I64, I64, ctypes.c_int, P, P, I32, P, P, P, ctypes.POINTER(I64)]),
+    ("pcg_pcmci_limits", I32, [ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32),
+                               ctypes.POINTER(D), ctypes.POINTER(D)]),
 ]
 
 _lib = None

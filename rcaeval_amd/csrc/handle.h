@@ -82,6 +82,12 @@ struct pcg_handle {
     // pcg_lingam_*: the working copy X_ and the standardized z (n x T each, column-major), one
     // step's D (n x n), and the column statistics / M / remaining-column lists
     DevBuf lingam_w, lingam_z, lingam_d, lingam_small;
+    // pcg_pcmci_*: the lag-expanded data E (T_eff x W, row-major), its correlation matrix R (W x W),
+    // the column flags / crit table / exact list / counters, and the exact path's designs. The
+    // (T, n, tau_max) R was computed for: pcg_pcmci_mci refuses any other
+    DevBuf pcmci_e, pcmci_r, pcmci_small, pcmci_work;
+    int64_t pcmci_shape[3] = {0, 0, 0};
+    bool pcmci_ok = false;
     DevBuf k1_digits;               // K1 int8 digit / residue planes of the centred X (corr.hip)
     // the (N, n, k, b) a CRT-mode pcg_corr_shard computed h->colmean's column exponents for;
     // pcg_corr_shard_finish refuses to rebuild C from exponents of any other call

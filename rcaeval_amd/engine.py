@@ -628,6 +628,92 @@ class Engine:
         order = order[:n].cpu().numpy()
         return (order, S.cpu().numpy()) if scores else order
 
+    # ------------------------------------------------------------------ PCMCI
+    def pcmci_limits(self) -> dict:
+        """The limits and fast-path guards of the PCMCI kernels (``pcg_pcmci_limits``)."""
+        from .graph_construction.pcmci import limits
+        return limits()
+
+    def pcmci_parents(self, X, tau_max: int, pc_alpha: float, check_status: bool = True) -> dict:
+        """PC1 of every target of a T x n array (``pcg_pcmci_parents``), which also leaves the
+        lag-expanded correlation matrix in the handle for ``pcmci_mci``. Host results: ``parents``
+        (per target the ordered list of ``(i, -lag)``), ``val_min`` (same shape), ``levels``,
+        ``tests``, ``status`` (n each) and ``exact_items``; ``ids`` / ``count`` are the device
+        arrays ``pcmci_mci`` takes. With ``check_status`` a status 1 (a constant window) or 2
+        (non-finite input) raises ``ValueError``."""
+        from .graph_construction import pcmci as pm
+        torch = _torch()
+        Xd, T, n, ldx = self._rows(X)
+        tau_max = int(tau_max)
+        lim = pm.limits()
+        pcap = lim["z_cap"] + 2
+        crit = np.ascontiguousarray(pm.critical_values(T - 2 * tau_max, float(pc_alpha), lim["z_cap"] + 1))
+        ids = torch.zeros((max(n, 1), pcap), dtype=torch.int32, device=self.device)
+        vmin = torch.zeros((max(n, 1), pcap), dtype=torch.float64, device=self.device)
+        k = [torch.zeros(max(n, 1), dtype=torch.int32, device=self.device) for _ in range(3)]     # count, levels, status
+        tests = torch.zeros(max(n, 1), dtype=torch.int64, device=self.device)
+        exact = ctypes.c_int64()
+        check(self.h, self.lib.pcg_pcmci_parents(
+            self.h, ctypes.c_void_p(Xd.data_ptr()), T, n, ldx, tau_max, crit.ctypes.data_as(ctypes.c_void_p), len(crit),
+            ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(vmin.data_ptr()), ctypes.c_void_p(k[0].data_ptr()), pcap,
+            ctypes.c_void_p(k[1].data_ptr()), ctypes.c_void_p(tests.data_ptr()), ctypes.c_void_p(k[2].data_ptr()),
+            ctypes.byref(exact)), "pcg_pcmci_parents")
+        count, levels, status = (t.cpu().numpy() for t in k)
+        out = {"ids": ids, "count": k[0], "pcap": pcap, "T": T, "n": n, "tau_max": tau_max, "levels": levels,
+               "tests": tests.cpu().numpy(), "status": status, "exact_items": int(exact.value)}
+        if check_status:
+            pm.raise_on_status(status)
+        ids_h, vmin_h = ids.cpu().numpy(), vmin.cpu().numpy()
+        K = 2 * tau_max + 1
+        out["parents"] = [[(int(q) // K, -(int(q) % K)) for q in ids_h[j, :min(count[j], pcap)]] for j in range(n)]
+        out["val_min"] = [[float(v) for v in vmin_h[j, :min(count[j], pcap)]] for j in range(n)]
+        return out
+
+    def pcmci_mci(self, T: int, n: int, tau_max: int, parents) -> dict:
+        """MCI on the correlation matrix the last ``pcmci_parents`` of the same (T, n, tau_max)
+        left in the handle (``pcg_pcmci_mci``). ``parents``: that call's result, or a list of n lists
+        of ``(i, -lag)``. Host arrays ``val``, ``dim`` (|Z|, -1 untested), ``status``, each
+        n x n x (tau_max + 1) indexed [i, j, tau], and ``exact_items``."""
+        torch = _torch()
+        tau_max, n, T = int(tau_max), int(n), int(T)
+        if isinstance(parents, dict):
+            ids, count, pcap = parents["ids"], parents["count"], parents["pcap"]
+        else:
+            K = 2 * tau_max + 1
+            pcap = max(1, max((len(p) for p in parents), default=1))
+            ids_h = np.zeros((n, pcap), dtype=np.int32)
+            cnt_h = np.zeros(n, dtype=np.int32)
+            for j, pl in enumerate(parents):
+                cnt_h[j] = len(pl)
+                for k, (i, neg) in enumerate(pl):
+                    ids_h[j, k] = int(i) * K - int(neg)
+            ids, count = torch.from_numpy(ids_h).to(self.device), torch.from_numpy(cnt_h).to(self.device)
+        shape = (n, n, tau_max + 1)
+        val = torch.zeros(shape, dtype=torch.float64, device=self.device)
+        dim = torch.zeros(shape, dtype=torch.int32, device=self.device)
+        st = torch.zeros(shape, dtype=torch.int32, device=self.device)
+        exact = ctypes.c_int64()
+        check(self.h, self.lib.pcg_pcmci_mci(self.h, T, n, tau_max, ctypes.c_void_p(ids.data_ptr()),
+                                             ctypes.c_void_p(count.data_ptr()), int(pcap), ctypes.c_void_p(val.data_ptr()),
+                                             ctypes.c_void_p(dim.data_ptr()), ctypes.c_void_p(st.data_ptr()),
+                                             ctypes.byref(exact)), "pcg_pcmci_mci")
+        return {"val": val.cpu().numpy(), "dim": dim.cpu().numpy(), "status": st.cpu().numpy(),
+                "exact_items": int(exact.value)}
+
+    def pcmci(self, X, tau_max: int, pc_alpha: float) -> dict:
+        """``run_pcmci(tau_max, pc_alpha)`` of a T x n array: ``val_matrix`` and ``p_matrix``
+        (n x n x (tau_max + 1), [i, j, tau]: column i at lag tau against column j), ``parents`` and
+        the counters (``levels``, ``tests`` per target, ``dim_matrix``, ``exact_items`` of PC1 and
+        MCI). Raises ``ValueError`` on a constant window or non-finite input."""
+        from .graph_construction import pcmci as pm
+        par = self.pcmci_parents(X, tau_max, pc_alpha)
+        mci = self.pcmci_mci(par["T"], par["n"], par["tau_max"], par)
+        pm.raise_on_status(mci["status"])
+        val, p = pm.matrices_from_stats(mci["val"], mci["dim"], par["T"] - 2 * par["tau_max"])
+        return {"val_matrix": val, "p_matrix": p, "dim_matrix": mci["dim"], "parents": par["parents"],
+                "val_min": par["val_min"], "levels": par["levels"], "tests": par["tests"], "status": mci["status"],
+                "exact_items": {"parents": par["exact_items"], "mci": mci["exact_items"]}}
+
     # ------------------------------------------------------------------ K4
     def pagerank_dense(self, A, damping: float = 0.85, n_iter: int = 10, tol: float = 1e-6) -> np.ndarray:
         torch = _torch()

@@ -1,0 +1,252 @@
+"""GPU: pcg_pcmci_parents / pcg_pcmci_mci, the pcmci graph learner and microcause against the
+numpy/scipy restatement of the tigramite contract (tests/pcmci_ref.py).
+
+Tolerance of every ParCorr value (``val_min``, ``val_matrix``): B + 10 * delta absolute.
+B = ``fast_path_bound(zmax)`` is the documented bound of an accepted fast-path value (DESIGN.md,
+"PCMCI") at the largest |Z| the restatement met on the input; delta is the restatement's own
+uncertainty on that input, the largest difference between its lstsq and QR solves. Nothing in the
+tolerance comes from the engine's output.
+
+Parent lists, level and test counts and |Z| are compared exactly, which needs every decision to be
+stable under that tolerance. The seeds in ``CASES`` are chosen per shape so that the restatement
+alone satisfies the preconditions, each asserted here: no PC1 or final p within 1e-6 relative of
+pc_alpha, 0.001 or the 0.0005 rounding edge; consecutive sorted val_min values at least
+1e3 * tolerance apart; every |Z| within the kernel's cap; no constant window.
+
+Worst observed |error| / tolerance over the five shapes: see DESIGN.md, "PCMCI".
+"""
+import functools
+
+import numpy as np
+import pandas as pd
+import pytest
+
+import pcmci_ref as pr
+from rcaeval_amd import _lib
+from rcaeval_amd.graph_construction import pcmci as pmod
+
+pytestmark = pytest.mark.gpu
+
+# (T, n, tau_max, pc_alpha, seed): 252 = 12 * 21 columns take the digit K1, 273 = 13 * 21 the CRT K1
+CASES = [(30, 2, 1, 0.2, 0), (60, 3, 2, 0.2, 5), (200, 7, 3, 0.2, 6), (300, 12, 10, 0.1, 5), (300, 13, 10, 0.1, 2)]
+IDS = ["%dx%d-tau%d" % c[:3] for c in CASES]
+
+
+def _eng():
+    from rcaeval_amd.engine import get_engine
+    return get_engine(0)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _engine_first():
+    """The engine (and with it torch's HIP runtime) is created before anything else loads the library."""
+    _eng()
+
+
+def _tol(ref):
+    zmax = pr.preconditions(ref, 0.0)["zmax"]
+    return pmod.fast_path_bound(zmax) + 10.0 * ref["delta"]
+
+
+@functools.lru_cache(maxsize=None)
+def _engine(case):
+    ref = pr.case(*case)
+    return _eng().pcmci(ref["X"].copy(), case[2], case[3])
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_restatement_preconditions(case):
+    ref = pr.case(*case)
+    tol = _tol(ref)
+    pre = pr.preconditions(ref, tol)
+    print(f"preconditions {case}: {pre} tol {tol:.3e} delta {ref['delta']:.2e}")
+    assert pre["rel_p"] > 1e-6
+    assert pre["gap"] >= 1e3 * tol
+    assert pre["zmax"] <= pmod.limits()["z_cap"]
+    assert not ref["constant"]
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_parents_levels_and_counts_equal_the_restatement(case):
+    ref, out = pr.case(*case), _engine(case)
+    assert out["parents"] == ref["parents"]
+    assert [int(v) for v in out["levels"]] == [r["levels"] for r in ref["pc1"]]
+    assert [int(v) for v in out["tests"]] == [r["tests"] for r in ref["pc1"]]
+    np.testing.assert_array_equal(out["dim_matrix"], ref["dim_matrix"])
+    if case[0] == 300:          # the deep shapes: several levels, candidates inside the top d, re-sorts
+        assert max(r["levels"] for r in ref["pc1"]) >= 7 and max(len(p) for p in ref["parents"]) >= 6
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_values_within_the_documented_bound(case):
+    ref, out = pr.case(*case), _engine(case)
+    tol = _tol(ref)
+    worst = 0.0
+    for got, r in zip(out["val_min"], ref["pc1"]):
+        if r["val_min"]:
+            worst = max(worst, float(np.max(np.abs(np.asarray(got) - np.asarray(r["val_min"])))))
+    worst = max(worst, float(np.max(np.abs(out["val_matrix"] - ref["val_matrix"]))))
+    print(f"values {case}: worst |error| {worst:.3e} tolerance {tol:.3e} ratio {worst / tol:.3e}")
+    assert worst <= tol
+    # the VAR input leaves nothing on the exact path
+    assert out["exact_items"] == {"parents": 0, "mci": 0}
+    assert set(np.unique(out["status"])) == {0}
+
+
+def _p_bound(val, dim, T_eff, tol):
+    """|dp| <= 2 * |dp / dval| * tol of p = 2 t.sf(|val| sqrt(f / (1 - val^2)), f), to first order."""
+    from scipy import stats
+    f = np.maximum(T_eff - 2.0 - dim, 1.0)
+    t = np.abs(val) * np.sqrt(f / (1.0 - val * val))
+    return 2.0 * (2.0 * stats.t.pdf(t, f) * np.sqrt(f) / (1.0 - val * val) ** 1.5) * tol + 1e-300
+
+
+@pytest.mark.parametrize("case", CASES, ids=IDS)
+def test_p_matrix_and_adjacency_equal_the_restatement(case):
+    ref, out = pr.case(*case), _engine(case)
+    bound = _p_bound(ref["val_matrix"], ref["dim_matrix"], ref["T_eff"], _tol(ref))
+    assert (np.abs(out["p_matrix"] - ref["p_matrix"]) <= bound).all()
+    adj, link = pmod.adjacency_from_p(out["p_matrix"])
+    np.testing.assert_array_equal(link, ref["link"])
+    np.testing.assert_array_equal(adj, ref["adj"])
+    T, n, tau_max, alpha, _ = case
+    df = pd.DataFrame(ref["X"], columns=[f"c{k}" for k in range(n)])
+    np.testing.assert_array_equal(pmod.pcmci(df, tau_max=tau_max, alpha=alpha), ref["adj"])
+
+
+@pytest.mark.parametrize("case", CASES[1:4], ids=IDS[1:4])
+def test_mci_alone_on_the_restatement_parents(case):
+    """pcg_pcmci_mci fed the restatement's parents: the second kernel without the first's lists."""
+    ref = pr.case(*case)
+    T, n, tau_max, alpha, _ = case
+    eng = _eng()
+    eng.pcmci_parents(ref["X"].copy(), tau_max, alpha)             # leaves R in the handle
+    out = eng.pcmci_mci(T, n, tau_max, ref["parents"])
+    np.testing.assert_array_equal(out["dim"], ref["dim_matrix"])
+    val, p = pmod.matrices_from_stats(out["val"], out["dim"], ref["T_eff"])
+    assert np.max(np.abs(val - ref["val_matrix"])) <= _tol(ref)
+    np.testing.assert_array_equal(pmod.adjacency_from_p(p)[0], ref["adj"])
+    assert out["exact_items"] == 0
+
+
+def test_leading_dimension():
+    import torch
+    case = CASES[1]
+    ref = pr.case(*case)
+    T, n, tau_max, alpha, _ = case
+    eng = _eng()
+    wide = torch.full((T, n + 3), float("nan"), dtype=torch.float64, device=eng.device)
+    wide[:, :n] = torch.from_numpy(ref["X"]).to(eng.device)
+    out = eng.pcmci(wide[:, :n], tau_max, alpha)
+    assert out["parents"] == ref["parents"]
+    assert np.max(np.abs(out["val_matrix"] - ref["val_matrix"])) <= _tol(ref)
+
+
+def test_near_collinear_lags_take_the_exact_path():
+    """Doubly integrated noise: neighbouring lags of a column are collinear to ~1e-4, below the
+    pivot guard, so items go to the QR path, and still meet the tolerance."""
+    T, n, tau_max, alpha = 120, 3, 2, 0.2
+    ref = pr.case(T, n, tau_max, alpha, 1, "collinear")
+    tol = _tol(ref)
+    assert not ref["constant"]
+    eng = _eng()
+    par = eng.pcmci_parents(ref["X"].copy(), tau_max, alpha)
+    out = eng.pcmci_mci(T, n, tau_max, ref["parents"])
+    assert par["exact_items"] > 0 and out["exact_items"] > 0 and (out["status"] == 3).sum() == out["exact_items"]
+    assert set(np.unique(out["status"])) <= {0, 3}
+    np.testing.assert_array_equal(out["dim"], ref["dim_matrix"])
+    val, _ = pmod.matrices_from_stats(out["val"], out["dim"], ref["T_eff"])
+    err = float(np.max(np.abs(val - ref["val_matrix"])))
+    print(f"collinear: exact items PC1 {par['exact_items']} MCI {out['exact_items']} worst |error| {err:.3e} "
+          f"tolerance {tol:.3e} delta {ref['delta']:.2e}")
+    assert err <= tol
+    pre = pr.preconditions(ref, tol)
+    assert pre["rel_p"] > 1e-6 and pre["gap"] >= 1e3 * tol         # PC1's decisions are stable too
+    assert par["parents"] == ref["parents"]
+    for got, r in zip(par["val_min"], ref["pc1"]):
+        assert np.max(np.abs(np.asarray(got) - np.asarray(r["val_min"])), initial=0.0) <= tol
+
+
+def test_constant_window_gives_status_1_and_value_error():
+    X = pr.gen_var(80, 4, 2, 3)
+    X[1:, 2] = 1.5                                           # constant over every window it enters, not over the frame
+    eng = _eng()
+    par = eng.pcmci_parents(X, 2, 0.2, check_status=False)
+    assert (par["status"] == 1).all() and all(len(p) == 0 for p in par["parents"])
+    out = eng.pcmci_mci(80, 4, 2, [[(0, -1)], [(1, -1)], [(2, -1)], [(3, -1)]])
+    tested = out["dim"] >= 0                                # all but the (i, i, 0) entries
+    assert (out["status"][2][tested[2]] == 1).all() and (out["status"][:, 2][tested[:, 2]] == 1).all()
+    assert out["status"][0, 1, 1] == 0 and np.isfinite(out["val"][0, 1, 1]) and np.isnan(out["val"][2, 1, 1])
+    with pytest.raises(ValueError, match="constant"):
+        eng.pcmci(X, 2, 0.2)
+    with pytest.raises(ValueError, match="constant"):
+        pmod.pcmci(pd.DataFrame(X), tau_max=2, alpha=0.2)
+
+
+def test_non_finite_input_gives_status_2():
+    X = pr.gen_var(80, 4, 2, 3)
+    X[40, 1] = np.nan
+    eng = _eng()
+    par = eng.pcmci_parents(X, 2, 0.2, check_status=False)
+    assert (par["status"] == 2).all()
+    out = eng.pcmci_mci(80, 4, 2, [[(0, -1)], [(1, -1)], [(2, -1)], [(3, -1)]])
+    assert (out["status"][1][out["dim"][1] >= 0] == 2).all() and out["status"][0, 2, 1] == 0
+    with pytest.raises(ValueError, match="non-finite"):
+        eng.pcmci(X, 2, 0.2)
+
+
+def test_limits_are_refused_before_anything_is_read():
+    eng = _eng()
+    lib = _lib.load()
+    X = pr.gen_var(40, 3, 2, 0)
+
+    def parents(T, n, tau_max):       # null pointers: a refused call reads none of them
+        return lib.pcg_pcmci_parents(eng.h, None, T, n, n, tau_max, None, 63, None, None, None, 64, None, None, None, None)
+    assert parents(6, 3, 2) == _lib.PCG_ERR_DOMAIN              # T_eff = 2
+    assert parents(40, 3, 0) == _lib.PCG_ERR_INVALID
+    assert parents(40, 3, pmod.limits()["max_tau"] + 1) == _lib.PCG_ERR_INVALID
+    assert parents(400, 500, 10) == _lib.PCG_ERR_INVALID        # 10500 lag-expanded columns
+    assert parents(40, 3, 2) == _lib.PCG_ERR_INVALID            # null pointers
+    with pytest.raises(ValueError):
+        eng.pcmci(X[:6], 2, 0.2)
+    with pytest.raises(_lib.PcgError):
+        eng.pcmci(X, 17, 0.2)
+    eng.pcmci_parents(X, 2, 0.2)
+    with pytest.raises(_lib.PcgError):                          # R in the handle is of another shape
+        eng.pcmci_mci(40, 3, 1, [[], [], []])
+    out = eng.pcmci_mci(40, 3, 2, [[(0, -1), (7, -1)], [], []])     # a malformed parent entry: refused by status
+    assert (out["status"][1:, 0] == 4).all() and (out["status"][0, 1:] == 4).all() and out["status"][1, 2, 1] == 0
+
+
+def _frame(ref, n):
+    df = pd.DataFrame(ref["X"], columns=[f"s{k}_cpu" for k in range(n)])
+    df.insert(0, "time", np.arange(len(df)))
+    return df
+
+
+def test_microcause_equals_the_restatement():
+    from rcaeval_amd import e2e
+    case = CASES[3]                                             # tau_max = 10, pc_alpha = 0.1: the method's own
+    ref = pr.case(*case)
+    n = case[1]
+    names = [f"s{k}_cpu" for k in range(n)]
+    df = _frame(ref, n)
+    np.random.seed(0)
+    want = pr.microcause_ranks(ref["X"], names, ref["p_matrix"], "s3_cpu", epochs=20, walk_step=50)
+    np.random.seed(0)
+    got = e2e.microcause(df, 0, dataset="online-boutique", sli="s3_cpu", epochs=20, walk_step=50)
+    np.testing.assert_array_equal(got["adj"], want["adj"])
+    assert got["adj"].sum() > n and got["node_names"] == names
+    assert got["ranks"] == want["ranks"]
+
+
+def test_microcause_defaults_rank_every_node():
+    from rcaeval_amd import e2e
+    case = CASES[3]
+    ref = pr.case(*case)
+    n = case[1]
+    np.random.seed(1)
+    got = e2e.microcause(_frame(ref, n), 0, dataset="online-boutique", sli="s0_cpu")
+    assert sorted(got["ranks"]) == sorted(f"s{k}_cpu" for k in range(n)) and len(got["ranks"]) == n
+    with pytest.raises(ValueError):
+        e2e.microcause(_frame(ref, n), 0, dataset="online-boutique", sli="absent_cpu")

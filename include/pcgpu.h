@@ -595,6 +595,54 @@ int pcg_pcmci_mci(pcg_handle *h, int64_t T, int64_t n, int tau_max, const int32_
 int pcg_pcmci_limits(int32_t *max_tau, int32_t *z_cap, int32_t *max_width, int32_t *max_candidates,
                      double *tau, double *beta_c);
 
+/* ---- fGES linear-Gaussian score (fges, fges_pagerank, fges_randomwalk) -------------------
+ * Replaces the statsmodels.OLS fits of LIB/python/scores.py:142-171 (penalty = 2) behind
+ * LIB/libraries/FGES/fges_main.py and RCAEval/graph_construction/fges.py. The score change of
+ * adding x to the parents B of y is T g - 2 log T with g = log(SSR(y|B) / SSR(y|B + x)) =
+ * -log(1 - rho^2(x, y . B)), rho the partial correlation inside the ddof-0 correlation matrix R
+ * of the T x n data. The library computes g; the caller applies T and the penalty and runs the
+ * search.
+ *
+ * Limits (pcg_fges_limits; anything else is PCG_ERR_INVALID before anything is read): 1 <= n <=
+ * 8192, T >= 2, ldx >= n, T * 512 bytes of exact-path workspace <= 1 GiB; |B| <= 62 per group
+ * ({B, x, y} is factorised in 33 KB of LDS).
+ *
+ * Fast path and guards: R[B + y] is Cholesky-factored (unit diagonal) once per group. An item keeps
+ * the fast path's g only if every pivot of B, the residual variance s_xx of x given B and the
+ * residual variances of y given B and given B + x are >= tau, and the regression coefficients h of
+ * y on B + x (standardized units) have (1 + |h|_1)^2 <= beta_c; the documented error bound of such
+ * a g is 2 beta_c (|B| + 20) 2^-53 / tau. Anything else is recomputed by the exact path,
+ * Householder QR on the standardized (ddof 0) columns themselves, one block per item (a column
+ * dependent to lstsq's rank tolerance is skipped). Status of an item: 0 ok; 1 a column of the
+ * item is constant; 2 non-finite input; 3 ok, computed by the exact path; 4 refused: |B| above the
+ * cap, an id out of range, a duplicate id in B, x or y inside B, x == y, or malformed offsets
+ * (refused on the device, never used as an index). gain is NaN under 1, 2 and 4.
+ *
+ * pcg_fges_begin: standardizes the columns of X (device, T x n doubles, row stride ldx), computes
+ * R with pcg_corr's kernels and keeps both in the handle for pcg_fges_gains. gain0: device n x n
+ * doubles out, the depth-0 gains -log1p(-r^2) (one value per unordered pair, so symmetric; NaN on
+ * the diagonal and where a column is flagged; a pair with 1 - r^2 < tau is recomputed by the exact
+ * path with an empty base). status: device n int32 out, per column 0, 1 constant, 2 non-finite.
+ *
+ * pcg_fges_gains: a batch of groups in CSR form on the R of the last pcg_fges_begin (none:
+ * PCG_ERR_INVALID). Group k has the target grp_y[k], the base set base_ids[base_off[k] ..
+ * base_off[k + 1]) and the items item_off[k] .. item_off[k + 1), item i testing the candidate
+ * item_x[i]. All arrays are device int32; base_off and item_off have n_groups + 1 entries,
+ * base_ids n_base and item_x n_items. gain: device n_items doubles out; status: device n_items
+ * int32 out. exact_items: host out, the items the exact path computed, each counted once (may be
+ * NULL). Groups of up to 4 items (pcg_fges_limits: narrow_max) run one wave per group, wider ones
+ * on a 256-thread workgroup with the candidates spread over its waves. The caller lists the narrow
+ * groups first: groups 0 .. n_narrow - 1 have 1 .. 4 items, the rest more (a group without items
+ * may stand anywhere). Each kind gets a launch of its own size, none when it is empty; a group on
+ * the wrong side is refused like malformed offsets (status 4).                                    */
+int pcg_fges_begin(pcg_handle *h, const double *X, int64_t T, int64_t n, int64_t ldx, double *gain0,
+                   int32_t *status);
+int pcg_fges_gains(pcg_handle *h, int64_t n_groups, const int32_t *grp_y, const int32_t *base_off,
+                   const int32_t *base_ids, int64_t n_base, const int32_t *item_off, const int32_t *item_x,
+                   int64_t n_items, int64_t n_narrow, double *gain, int32_t *status, int64_t *exact_items);
+/* The limits and guards the fGES kernels were built with (host-only, any may be NULL).           */
+int pcg_fges_limits(int32_t *b_cap, int32_t *max_n, int32_t *narrow_max, double *tau, double *beta_c);
+
 #ifdef __cplusplus
 }
 #endif

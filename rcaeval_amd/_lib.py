@@ -183,6 +183,10 @@ SIGNATURES = [
     ("pcg_pcmci_mci", I32, [P, I64, I64, ctypes.c_int, P, P, I32, P, P, P, ctypes.POINTER(I64)]),
     ("pcg_pcmci_limits", I32, [ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32),
                                ctypes.POINTER(D), ctypes.POINTER(D)]),
+    ("pcg_fges_begin", I32, [P, P, I64, I64, I64, P, P]),
+    ("pcg_fges_gains", I32, [P, I64, P, P, P, I64, P, P, I64, I64, P, P, ctypes.POINTER(I64)]),
+    ("pcg_fges_limits", I32, [ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(D),
+                              ctypes.POINTER(D)]),
 ]
 
 _lib = None

@@ -88,6 +88,12 @@ struct pcg_handle {
     DevBuf pcmci_e, pcmci_r, pcmci_small, pcmci_work;
     int64_t pcmci_shape[3] = {0, 0, 0};
     bool pcmci_ok = false;
+    // pcg_fges_*: the standardized columns E (T x n, row-major), their correlation matrix R (n x n),
+    // the column flags and the exact-list counter, the exact list, and the exact path's designs.
+    // The (T, n) of the last pcg_fges_begin: pcg_fges_gains refuses to run without one
+    DevBuf fges_e, fges_r, fges_small, fges_list, fges_work;
+    int64_t fges_shape[2] = {0, 0};
+    bool fges_ok = false;
     DevBuf k1_digits;               // K1 int8 digit / residue planes of the centred X (corr.hip)
     // the (N, n, k, b) a CRT-mode pcg_corr_shard computed h->colmean's column exponents for;
     // pcg_corr_shard_finish refuses to rebuild C from exponents of any other call

@@ -48,10 +48,12 @@ from .circa import circa  # noqa: E402
 from .cloudranger import cloudranger  # noqa: E402
 from .pc_pagerank import pc_pagerank, pc_pagerank_batch  # noqa: E402
 from .fci_pagerank import fci_pagerank  # noqa: E402
+from .ges_pagerank import fges_pagerank, fges_randomwalk  # noqa: E402
 from .granger_pagerank import granger_pagerank  # noqa: E402
 from .lingam_pagerank import micro_diag  # noqa: E402
 from .microcause import microcause  # noqa: E402
 from .pc_randomwalk import fci_randomwalk, granger_randomwalk, pc_randomwalk  # noqa: E402
 
-__all__ = ["rca", "circa", "cloudranger", "fci_pagerank", "fci_randomwalk", "granger_pagerank", "granger_randomwalk",
-           "micro_diag", "microcause", "pc_pagerank", "pc_pagerank_batch", "pc_randomwalk"]
+__all__ = ["rca", "circa", "cloudranger", "fci_pagerank", "fci_randomwalk", "fges_pagerank", "fges_randomwalk",
+           "granger_pagerank", "granger_randomwalk", "micro_diag", "microcause", "pc_pagerank", "pc_pagerank_batch",
+           "pc_randomwalk"]

@@ -714,6 +714,83 @@ class Engine:
                 "val_min": par["val_min"], "levels": par["levels"], "tests": par["tests"], "status": mci["status"],
                 "exact_items": {"parents": par["exact_items"], "mci": mci["exact_items"]}}
 
+    # ------------------------------------------------------------------ fGES
+    def fges_limits(self) -> dict:
+        """The limits and fast-path guards of the fGES kernels (``pcg_fges_limits``)."""
+        from .graph_construction.fges import limits
+        return limits()
+
+    def fges_begin(self, X) -> dict:
+        """Standardize a T x n array, compute its correlation matrix and keep both in the handle
+        for ``fges_gains`` (``pcg_fges_begin``). Host results: ``gain0`` (n x n, the depth-0 gains
+        -log1p(-r^2), NaN on the diagonal and on flagged columns) and ``status`` (n: 0, 1 a
+        constant column, 2 non-finite)."""
+        torch = _torch()
+        Xd, T, n, ldx = self._rows(X)
+        g0 = torch.empty((max(n, 1), max(n, 1)), dtype=torch.float64, device=self.device)
+        st = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        check(self.h, self.lib.pcg_fges_begin(self.h, ctypes.c_void_p(Xd.data_ptr()), T, n, ldx,
+                                              ctypes.c_void_p(g0.data_ptr()), ctypes.c_void_p(st.data_ptr())),
+              "pcg_fges_begin")
+        return {"gain0": g0.cpu().numpy()[:n, :n], "status": st.cpu().numpy()[:n], "T": T, "n": n}
+
+    def fges_gains(self, groups) -> dict:
+        """g = log(SSR(y|B) / SSR(y|B + x)) for a batch of groups on the matrix the last
+        ``fges_begin`` left in the handle (``pcg_fges_gains``). ``groups``: a list of
+        ``(y, B, candidates)`` with B and the candidates sequences of column ids. Host arrays
+        ``gain`` and ``status`` (one entry per candidate, in the caller's order; 0 ok, 1 / 2 a
+        flagged column, 3 ok by the exact path, 4 refused) and ``exact_items``. The groups are sent
+        with the narrow ones (up to ``narrow_max`` candidates) first, as the library asks."""
+        from .graph_construction.fges import limits
+        narrow_max = limits()["narrow_max"]
+        G = len(groups)
+        sizes = np.fromiter((len(g[2]) for g in groups), dtype=np.int64, count=G)
+        order = np.argsort(sizes > narrow_max, kind="stable")
+        sent = [groups[k] for k in order]
+        ys = np.fromiter((g[0] for g in sent), dtype=np.int64, count=G)
+        boff = np.zeros(G + 1, dtype=np.int64)
+        ioff = np.zeros(G + 1, dtype=np.int64)
+        np.cumsum([len(g[1]) for g in sent], out=boff[1:])
+        np.cumsum(sizes[order], out=ioff[1:])
+        nb, ni = int(boff[-1]), int(ioff[-1])
+        base = np.fromiter((q for g in sent for q in g[1]), dtype=np.int64, count=nb)
+        items = np.fromiter((q for g in sent for q in g[2]), dtype=np.int64, count=ni)
+        i32 = np.iinfo(np.int32)
+        packed = np.concatenate([ys, boff, ioff, base, items])
+        if packed.size and (packed.min() < i32.min or packed.max() > i32.max):
+            raise ValueError("fges_gains: an id does not fit int32")
+        out = self.fges_gains_csr(ys, boff, base, ioff, items, n_narrow=int((sizes <= narrow_max).sum()))
+        # back to the caller's order of groups
+        start = np.zeros(G + 1, dtype=np.int64)
+        np.cumsum(sizes, out=start[1:])
+        back = np.empty(ni, dtype=np.int64)
+        for pos, k in enumerate(order):
+            back[start[k]:start[k + 1]] = np.arange(ioff[pos], ioff[pos + 1])
+        return {"gain": out["gain"][back], "status": out["status"][back], "exact_items": out["exact_items"]}
+
+    def fges_gains_csr(self, grp_y, base_off, base_ids, item_off, item_x, n_narrow, n_base=None, n_items=None) -> dict:
+        """``pcg_fges_gains`` on the caller's own CSR arrays (one upload, two result copies):
+        groups 0 .. n_narrow - 1 are the narrow ones."""
+        torch = _torch()
+        parts = [np.ascontiguousarray(a, dtype=np.int32).ravel() for a in (grp_y, base_off, item_off, base_ids, item_x)]
+        G = len(parts[0])
+        if len(parts[1]) != G + 1 or len(parts[2]) != G + 1:
+            raise ValueError("fges_gains: base_off and item_off need one entry more than grp_y")
+        nb = len(parts[3]) if n_base is None else int(n_base)
+        ni = len(parts[4]) if n_items is None else int(n_items)
+        if nb > len(parts[3]) or ni > len(parts[4]):
+            raise ValueError("fges_gains: n_base / n_items beyond the arrays")
+        dev = torch.from_numpy(np.concatenate(parts + [np.zeros(1, dtype=np.int32)])).to(self.device)
+        offs = np.cumsum([0] + [len(p) for p in parts])
+        ptr = [ctypes.c_void_p(dev.data_ptr() + 4 * int(o)) for o in offs[:5]]
+        gain = torch.empty(max(ni, 1), dtype=torch.float64, device=self.device)
+        st = torch.empty(max(ni, 1), dtype=torch.int32, device=self.device)
+        exact = ctypes.c_int64()
+        check(self.h, self.lib.pcg_fges_gains(self.h, G, ptr[0], ptr[1], ptr[3], nb, ptr[2], ptr[4], ni, int(n_narrow),
+                                              ctypes.c_void_p(gain.data_ptr()), ctypes.c_void_p(st.data_ptr()),
+                                              ctypes.byref(exact)), "pcg_fges_gains")
+        return {"gain": gain.cpu().numpy()[:ni], "status": st.cpu().numpy()[:ni], "exact_items": int(exact.value)}
+
     # ------------------------------------------------------------------ K4
     def pagerank_dense(self, A, damping: float = 0.85, n_iter: int = 10, tol: float = 1e-6) -> np.ndarray:
         torch = _torch()

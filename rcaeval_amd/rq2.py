@@ -44,11 +44,12 @@ DATASET_MAP = {                                   # rq2.py:135-144
 
 def methods():
     """Methods this engine serves (``rq2.py:36-59`` resolves them by name)."""
-    from .e2e import (circa, cloudranger, granger_pagerank, granger_randomwalk, micro_diag, microcause, pc_pagerank,
-                      pc_randomwalk)
+    from .e2e import (circa, cloudranger, fges_pagerank, fges_randomwalk, granger_pagerank, granger_randomwalk,
+                      micro_diag, microcause, pc_pagerank, pc_randomwalk)
     return {"pc_pagerank": pc_pagerank, "pc_randomwalk": pc_randomwalk, "cloudranger": cloudranger,
             "circa": circa, "granger_pagerank": granger_pagerank, "granger_randomwalk": granger_randomwalk,
-            "micro_diag": micro_diag, "microcause": microcause}
+            "micro_diag": micro_diag, "microcause": microcause, "fges_pagerank": fges_pagerank,
+            "fges_randomwalk": fges_randomwalk}
 
 
 def dump_json(filename: str, data) -> None:

@@ -22,11 +22,14 @@
 //                 33 KB work matrix per workgroup leaves the one-wave kind at one wave per SIMD
 //                 (four groups per CU): these batches are bound by launch latency, not occupancy.
 //   k_fg_exact    the exact path: Householder QR on the columns of E themselves, one block per item.
+// The block sums, the column classification, the Cholesky of the fast path (chol_eliminate) and the
+// QR of the exact path (qr_eliminate) are dense_dev.h's, shared with pcmci.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 
+#include "dense_dev.h"
 #include "handle.h"
 
 namespace {
@@ -44,28 +47,11 @@ constexpr double FG_BETA_C = 400.0;
 constexpr int64_t FG_WS_BYTES = (int64_t)1 << 30;    // exact path: design workspace bound
 constexpr int FG_EXACT_BLOCKS = 256;
 
-__device__ inline double fg_wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the block's FG_BLOCK threads; every thread gets the total. red: FG_BLOCK / 64 doubles of LDS
-__device__ inline double fg_block_sum(double v, double *red) {
-    v = fg_wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int w = 0; w < FG_BLOCK / 64; ++w) s += red[w];
-    __syncthreads();
-    return s;
-}
-
 __global__ __launch_bounds__(FG_BLOCK) void k_fg_cols(const double *X, int64_t T, int n, int64_t ldx, int32_t *flags,
                                                       int32_t *status, double *E) {
     __shared__ double red[FG_BLOCK / 64];
     __shared__ double mm[3 * (FG_BLOCK / 64)];
-    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c = blockIdx.x, tid = threadIdx.x;
     const double *x = X + c;
     double lo = INFINITY, hi = -INFINITY, bad = 0.0, s = 0.0;
     for (int64_t r = tid; r < T; r += FG_BLOCK) {
@@ -77,31 +63,15 @@ __global__ __launch_bounds__(FG_BLOCK) void k_fg_cols(const double *X, int64_t T
         } else
             bad = 1.0;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fmin(lo, __shfl_xor(lo, o, 64));
-        hi = fmax(hi, __shfl_xor(hi, o, 64));
-        bad = fmax(bad, __shfl_xor(bad, o, 64));
-    }
-    if (lane == 0) {
-        mm[wave * 3] = lo;
-        mm[wave * 3 + 1] = hi;
-        mm[wave * 3 + 2] = bad;
-    }
-    __syncthreads();
-    for (int w = 0; w < FG_BLOCK / 64; ++w) {
-        lo = fmin(lo, mm[w * 3]);
-        hi = fmax(hi, mm[w * 3 + 1]);
-        bad = fmax(bad, mm[w * 3 + 2]);
-    }
-    const int fl = bad > 0.0 ? 2 : (lo == hi ? 1 : 0);      // block-uniform
-    const double mu = fg_block_sum(s, red) / (double)T;
+    const int fl = column_class<FG_BLOCK>(lo, hi, bad, mm);   // block-uniform
+    const double mu = block_sum<FG_BLOCK>(s, red) / (double)T;
     double q = 0.0;
     if (!fl)
         for (int64_t r = tid; r < T; r += FG_BLOCK) {
             const double v = x[r * ldx] - mu;
             q = fma(v, v, q);
         }
-    const double isd = 1.0 / sqrt(fg_block_sum(q, red) / (double)T);
+    const double isd = 1.0 / sqrt(block_sum<FG_BLOCK>(q, red) / (double)T);
     for (int64_t r = tid; r < T; r += FG_BLOCK) E[r * n + c] = fl ? ((r & 1) ? 1.0 : -1.0) : (x[r * ldx] - mu) * isd;
     if (tid == 0) {
         flags[c] = fl;
@@ -134,43 +104,9 @@ __global__ __launch_bounds__(FG_BLOCK) void k_fg_fill(int64_t n_items, double *g
     }
 }
 
-// Gather the lower triangle of R[cols, cols] (m x m, unit diagonal) into A and eliminate its first d
-// columns (right-looking Cholesky). On return row d holds y's row of the factor in columns < d and
-// the residual variance of y given B at (d, d). False (block-uniform) when a pivot is below FG_TAU.
-// Starts with a barrier: A and cols may have just been written / read.
-template <int NT>
-__device__ bool fg_factor(const double *R, int n, const int *cols, int m, int d, double *A) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    for (int idx = tid; idx < m * m; idx += NT) {
-        const int r = idx / m, c = idx % m;
-        if (c <= r) A[r * FG_LD + c] = r == c ? 1.0 : R[(int64_t)cols[r] * n + cols[c]];
-    }
-    bool ok = true;
-    for (int k = 0; k < d; ++k) {
-        __syncthreads();
-        const double piv = A[k * FG_LD + k];
-        if (!(piv >= FG_TAU)) {                // block-uniform
-            ok = false;
-            break;
-        }
-        const double lkk = sqrt(piv), ik = 1.0 / lkk;
-        __syncthreads();                       // everyone has read the pivot
-        for (int r = k + 1 + tid; r < m; r += NT) A[r * FG_LD + k] *= ik;
-        if (tid == 0) A[k * FG_LD + k] = lkk;
-        __syncthreads();
-        const int w = m - k - 1;
-        for (int idx = tid; idx < w * w; idx += NT) {
-            const int r = k + 1 + idx / w, c = k + 1 + idx % w;
-            if (c <= r) A[r * FG_LD + c] -= A[r * FG_LD + k] * A[c * FG_LD + k];
-        }
-    }
-    __syncthreads();
-    return ok;
-}
-
 // |g|_1 of g = L^-T w over one wave: lane k < d enters with entry k of the factor row w; column
-// oriented back substitution, lane r reads L(k, r). Every lane returns the norm.
+// oriented back substitution, lane r reads L(k, r). Every lane returns the norm. Not shared with
+// pcmci.hip's one-thread form, nor are k_fg_groups' lane-per-row solves: another launch shape.
 __device__ inline double fg_coef_norm1(const double *A, double w, int d, int lane) {
     double n1 = 0.0;
     for (int k = d - 1; k >= 0; --k) {
@@ -234,7 +170,7 @@ __global__ __launch_bounds__(NT) void k_fg_groups(const double *R, int n, const 
         bool shared_ok = false;
         double syy = 0.0, n1y = 0.0;
         if (!gfl) {                                                       // block-uniform
-            shared_ok = fg_factor<NT>(R, n, cols, d + 1, d, A);
+            shared_ok = chol_eliminate<NT, FG_LD>(R, n, cols, d + 1, d, A, FG_TAU);
             if (shared_ok) {
                 syy = A[d * FG_LD + d];
                 if (wave == 0) {
@@ -265,8 +201,8 @@ __global__ __launch_bounds__(NT) void k_fg_groups(const double *R, int n, const 
                     if (lane == c) b = bc;
                     if (lane > c && lane < d) v -= A[lane * FG_LD + c] * bc;
                 }
-                const double sxx = 1.0 - fg_wave_sum(b * b);
-                const double sxy = rx[y] - fg_wave_sum(lane < d ? b * A[d * FG_LD + lane] : 0.0);
+                const double sxx = 1.0 - wave_sum(b * b);
+                const double sxy = rx[y] - wave_sum(lane < d ? b * A[d * FG_LD + lane] : 0.0);
                 const double n1x = fg_coef_norm1(A, b, d, lane);
                 const double gamma = sxy / sxx, syyx = syy - sxy * gamma;
                 const double h1 = 1.0 + n1y + fabs(gamma) * (1.0 + n1x);
@@ -293,10 +229,9 @@ __global__ __launch_bounds__(NT) void k_fg_groups(const double *R, int n, const 
 }
 
 // One item on the exact path: the columns cols = [B (d), x, y] of E (already standardized) into the
-// block's workspace Aw (column-major, m x T), Householder QR over the B columns, then over x, with
-// block-wide reductions (a column whose remaining norm is below lstsq's rank tolerance is skipped,
-// which is the minimum-norm least-squares residual); g = log of the ratio of y's remaining sums of
-// squares before and after x. Each thread owns the rows r = tid, tid + FG_BLOCK, ..
+// block's workspace Aw (column-major, m x T), Householder QR over the B columns, then over x
+// (dense_dev.h's qr_eliminate: a dependent column is skipped); g = log of the ratio of y's remaining
+// sums of squares before and after x. Each thread owns the rows r = tid, tid + FG_BLOCK, ..
 __device__ double fg_exact_item(const double *E, int64_t T, int n, const int *cols, int d, double *Aw, double *red) {
     const int tid = threadIdx.x, m = d + 2;
     __syncthreads();
@@ -307,41 +242,16 @@ __device__ double fg_exact_item(const double *E, int64_t T, int n, const int *co
     }
     const double tol = (double)std::max<int64_t>(T, m) * 2.220446049250313e-16;
     const double *ay = Aw + (int64_t)(d + 1) * T;
-    int64_t rdone = 0;
-    double syy = 0.0;
-    for (int k = 0; k <= d; ++k) {
-        if (k == d) {                                              // B is eliminated: SSR(y | B)
-            for (int64_t r = tid; r < T; r += FG_BLOCK)
-                if (r >= rdone) syy = fma(ay[r], ay[r], syy);
-            syy = fg_block_sum(syy, red);
-        }
-        const double *ak = Aw + (int64_t)k * T;
-        double n0 = 0.0, n1 = 0.0;
-        for (int64_t r = tid; r < T; r += FG_BLOCK)
-            if (r >= rdone) {
-                const double v = ak[r];
-                n0 = fma(v, v, n0);
-                if (r == rdone) n1 = v;
-            }
-        n0 = fg_block_sum(n0, red);
-        n1 = fg_block_sum(n1, red);
-        if (!(n0 > tol * tol * (double)T)) continue;               // block-uniform: dependent column
-        const double alpha = -copysign(sqrt(n0), n1), vr = n1 - alpha, vn2 = 2.0 * (n0 - n1 * alpha);
-        for (int u = k + 1; u < m; ++u) {
-            double *au = Aw + (int64_t)u * T;
-            double dot = 0.0;
-            for (int64_t r = tid; r < T; r += FG_BLOCK)
-                if (r >= rdone) dot = fma(r == rdone ? vr : ak[r], au[r], dot);
-            const double f = 2.0 * fg_block_sum(dot, red) / vn2;
-            for (int64_t r = tid; r < T; r += FG_BLOCK)
-                if (r >= rdone) au[r] -= f * (r == rdone ? vr : ak[r]);
-        }
-        ++rdone;
-    }
+    int64_t rdone = qr_eliminate<FG_BLOCK>(Aw, T, m, 0, d, 0, tol, red);
+    double syy = 0.0;                                              // B is eliminated: SSR(y | B)
+    for (int64_t r = tid; r < T; r += FG_BLOCK)
+        if (r >= rdone) syy = fma(ay[r], ay[r], syy);
+    syy = block_sum<FG_BLOCK>(syy, red);
+    rdone = qr_eliminate<FG_BLOCK>(Aw, T, m, d, d + 1, rdone, tol, red);
     double syyx = 0.0;
     for (int64_t r = tid; r < T; r += FG_BLOCK)
         if (r >= rdone) syyx = fma(ay[r], ay[r], syyx);
-    syyx = fg_block_sum(syyx, red);
+    syyx = block_sum<FG_BLOCK>(syyx, red);
     return log(syy / syyx);
 }
 
@@ -399,9 +309,10 @@ struct FgSmall {
     unsigned int *counter;
 };
 bool fg_small(pcg_handle *h, int64_t n, FgSmall &s) {
-    const size_t o_ctr = ((size_t)n * 4 + 255) & ~(size_t)255;
-    if (!pcg_ensure(h, h->fges_small, o_ctr + 256)) return false;
-    s.flags = (int32_t *)h->fges_small.p;
+    Carve cv;
+    const size_t o_flags = cv.take((size_t)n * 4), o_ctr = cv.take(4);
+    if (!pcg_ensure(h, h->fges_small, cv.total)) return false;
+    s.flags = (int32_t *)((char *)h->fges_small.p + o_flags);
     s.counter = (unsigned int *)((char *)h->fges_small.p + o_ctr);
     return true;
 }
@@ -442,11 +353,10 @@ extern "C" int pcg_fges_begin(pcg_handle *h, const double *X, int64_t T, int64_t
     hipLaunchKernelGGL(k_fg_gain0, dim3(gb), dim3(FG_BLOCK), 0, h->stream, (const double *)R, (int)n,
                        (const int32_t *)s.flags, gain0, s.counter);
     PCG_HIP(h, hipGetLastError());
-    unsigned int left = 0;
-    PCG_HIP(h, hipMemcpyAsync(&left, s.counter, 4, hipMemcpyDeviceToHost, h->stream));
-    PCG_HIP(h, hipStreamSynchronize(h->stream));
+    int64_t left = 0;                                             // pairs i < j, counted and not listed
+    if (int rc1 = pcg_read_counter(h, "pcg_fges_begin", s.counter, n * n, &left)) return rc1;
     if (left) {                                                   // near-duplicate columns: rare
-        const int64_t eblocks = std::min<int64_t>((int64_t)left, FG_EXACT_BLOCKS), slot = 2 * T;
+        const int64_t eblocks = std::min<int64_t>(left, FG_EXACT_BLOCKS), slot = 2 * T;
         if (!pcg_ensure(h, h->fges_work, (size_t)(eblocks * slot * 8)))
             return pcg_fail(h, PCG_ERR_OOM, "pcg_fges_begin: exact-path workspace");
         hipLaunchKernelGGL(k_fg_gain0_exact, dim3((unsigned)eblocks), dim3(FG_BLOCK), 0, h->stream, (const double *)R,
@@ -496,19 +406,17 @@ extern "C" int pcg_fges_gains(pcg_handle *h, int64_t n_groups, const int32_t *gr
                                in, gain, status, list, s.counter, n_narrow, n_groups);
             PCG_HIP(h, hipGetLastError());
         }
-        unsigned int marked = 0;
-        PCG_HIP(h, hipMemcpyAsync(&marked, s.counter, 4, hipMemcpyDeviceToHost, h->stream));
-        PCG_HIP(h, hipStreamSynchronize(h->stream));
-        if ((int64_t)marked > n_items) return pcg_fail(h, PCG_ERR_HIP, "pcg_fges_gains: exact list overran (%u)", marked);
+        int64_t marked = 0;
+        if (int rc = pcg_read_counter(h, "pcg_fges_gains", s.counter, n_items, &marked)) return rc;
         if (marked) {
-            const int64_t eblocks = std::min<int64_t>({(int64_t)marked, (int64_t)FG_EXACT_BLOCKS, FG_WS_BYTES / (slot * 8)});
+            const int64_t eblocks = std::min<int64_t>({marked, (int64_t)FG_EXACT_BLOCKS, FG_WS_BYTES / (slot * 8)});
             if (!pcg_ensure(h, h->fges_work, (size_t)(eblocks * slot * 8)))
                 return pcg_fail(h, PCG_ERR_OOM, "pcg_fges_gains: exact-path workspace");
             hipLaunchKernelGGL(k_fg_exact, dim3((unsigned)eblocks), dim3(FG_BLOCK), 0, h->stream, (const double *)h->fges_e.p,
-                               T, (int)n, in, (const int32_t *)list, (int64_t)marked, (double *)h->fges_work.p, slot, gain);
+                               T, (int)n, in, (const int32_t *)list, marked, (double *)h->fges_work.p, slot, gain);
             PCG_HIP(h, hipGetLastError());
         }
-        if (exact_items) *exact_items = (int64_t)marked;
+        if (exact_items) *exact_items = marked;
     }
     PCG_HIP(h, hipStreamSynchronize(h->stream));
     return PCG_OK;

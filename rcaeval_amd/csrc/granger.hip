@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "dense_dev.h"
 #include "handle.h"
 
 namespace {
@@ -52,48 +53,6 @@ __host__ __device__ constexpr int gr_lagmask(int L) { return ((1 << L) - 1) << (
 // index of the auto-moment sum z_{t-a} z_{t-b} (a <= b) in a column's statistics
 __host__ __device__ constexpr int gr_pidx(int a, int b) { return 4 + a * 4 - a * (a - 1) / 2 + (b - a); }
 
-__device__ inline double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum of K per-thread values over the block; every thread gets the same totals. red: K * GR_WAVES
-template <int K>
-__device__ inline void block_sum(double (&v)[K], double *red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) red[k * GR_WAVES + wave] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double s = 0.0;
-        for (int w = 0; w < GR_WAVES; ++w) s += red[k * GR_WAVES + w];
-        v[k] = s;
-    }
-    __syncthreads();
-}
-
-__device__ inline void block_minmax(double &lo, double &hi, double *red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fmin(lo, __shfl_xor(lo, o, 64));
-        hi = fmax(hi, __shfl_xor(hi, o, 64));
-    }
-    if (lane == 0) {
-        red[wave] = lo;
-        red[GR_WAVES + wave] = hi;
-    }
-    __syncthreads();
-    for (int w = 0; w < GR_WAVES; ++w) {
-        lo = fmin(lo, red[w]);
-        hi = fmax(hi, red[GR_WAVES + w]);
-    }
-    __syncthreads();
-}
-
 // ---- column pass -------------------------------------------------------------------------------
 // cs[c]: [0..3] sums of z_{t-k} over t = 3..T-1, [4..13] sums of z_{t-a} z_{t-b} (gr_pidx), [14] mean
 __global__ __launch_bounds__(GR_BLOCK) void k_granger_cols(const double *X, int64_t T, int n, int64_t ldx, double *Zt,
@@ -112,7 +71,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_granger_cols(const double *X, int6
             hi = fmax(hi, v);
         }
     }
-    block_sum<2>(a1, red);
+    block_sum<GR_BLOCK>(a1, red);
     if (a1[1] > 0.0) {                         // block-uniform
         for (int64_t t = tid; t < T; t += GR_BLOCK) Zt[(int64_t)c * T + t] = __builtin_nan("");
         if (tid == 0) {
@@ -139,8 +98,8 @@ __global__ __launch_bounds__(GR_BLOCK) void k_granger_cols(const double *X, int6
             for (int b = a; b < 4; ++b) m[gr_pidx(a, b)] = fma(z[a], z[b], m[gr_pidx(a, b)]);
         }
     }
-    block_sum<14>(m, red);
-    block_minmax(lo, hi, red);
+    block_sum<GR_BLOCK>(m, red);
+    block_minmax<GR_BLOCK>(lo, hi, red);
     if (tid == 0) {
         for (int k = 0; k < 14; ++k) cs[(int64_t)c * GR_CS + k] = m[k];
         cs[(int64_t)c * GR_CS + 14] = mean;
@@ -370,6 +329,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_granger_pairs(const double *Zt, in
 // One block per listed item, each thread owning the rows r = tid, tid + 256, .. of the item's
 // design for the whole factorisation (so no thread ever reads a row another thread wrote).
 // A: the block's workspace slot, column-major M x nobs: [y_{t-1..L}, x_{t-1..L}, y_t] centred.
+// Not dense_dev.h's qr_eliminate: up to 7 columns per row pass, rank test scaled by the column's own norm.
 __global__ __launch_bounds__(GR_BLOCK) void k_granger_exact(const double *Zt, int64_t T, int n, int maxlag,
                                                             const int32_t *list, int64_t count, double *work,
                                                             int64_t slot, GrOut out) {
@@ -395,7 +355,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_granger_exact(const double *Zt, in
 #pragma unroll
             for (int u = 0; u < 7; ++u)
                 if (u < M) mu[u] += src(u, r);
-        block_sum<7>(mu, red);
+        block_sum<GR_BLOCK>(mu, red);
 #pragma unroll
         for (int u = 0; u < 7; ++u) {
             mu[u] /= (double)nobs;
@@ -409,7 +369,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_granger_exact(const double *Zt, in
                     A[(int64_t)u * nobs + r] = v;
                     cn[u] = fma(v, v, cn[u]);
                 }
-        block_sum<7>(cn, red);
+        block_sum<GR_BLOCK>(cn, red);
         const double tol = (double)std::max<int64_t>(nobs, M) * 2.220446049250313e-16;
         const double *yc = A + (int64_t)(M - 1) * nobs;
         int rdone = 0;                          // reflectors applied so far = rank of the lag columns
@@ -423,7 +383,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_granger_exact(const double *Zt, in
                     nv[0] = fma(v, v, nv[0]);
                     if (r == rdone) nv[1] = v;
                 }
-            block_sum<2>(nv, red);
+            block_sum<GR_BLOCK>(nv, red);
             double cnk = 0.0;
 #pragma unroll
             for (int u = 0; u < 7; ++u)
@@ -442,7 +402,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_granger_exact(const double *Zt, in
                         for (int u = 0; u < 7; ++u)
                             if (u > k && u < M) dot[u] = fma(v, A[(int64_t)u * nobs + r], dot[u]);
                     }
-                block_sum<7>(dot, red);
+                block_sum<GR_BLOCK>(dot, red);
                 for (int64_t r = tid; r < nobs; r += GR_BLOCK)
                     if (r >= rdone) {
                         const double v = r == rdone ? vr : ak[r];
@@ -456,7 +416,7 @@ __global__ __launch_bounds__(GR_BLOCK) void k_granger_exact(const double *Zt, in
                 double t2[1] = {0.0};
                 for (int64_t r = tid; r < nobs; r += GR_BLOCK)
                     if (r >= rdone) t2[0] = fma(yc[r], yc[r], t2[0]);
-                block_sum<1>(t2, red);
+                block_sum<GR_BLOCK>(t2, red);
                 if (k == L - 1) ssr_r = t2[0];
                 else ssr_u = t2[0];
             }
@@ -501,16 +461,11 @@ extern "C" int pcg_granger(pcg_handle *h, const double *X, int64_t T, int64_t n,
     PCG_HIP(h, hipSetDevice(h->device));
     const int64_t items = n * n * maxlag;
     // scratch: Z (n x T) | column statistics | column bits | exact list | its counter
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t o_z = take((size_t)n * T * 8), o_cs = take((size_t)n * GR_CS * 8),
-                 o_bits = take((size_t)n * 4), o_list = take((size_t)items * 4), o_ctr = take(4);
-    if (!pcg_ensure(h, h->granger_scratch, off))
-        return pcg_fail(h, PCG_ERR_OOM, "pcg_granger: scratch (%lld B)", (long long)off);
+    Carve cv;
+    const size_t o_z = cv.take((size_t)n * T * 8), o_cs = cv.take((size_t)n * GR_CS * 8),
+                 o_bits = cv.take((size_t)n * 4), o_list = cv.take((size_t)items * 4), o_ctr = cv.take(4);
+    if (!pcg_ensure(h, h->granger_scratch, cv.total))
+        return pcg_fail(h, PCG_ERR_OOM, "pcg_granger: scratch (%lld B)", (long long)cv.total);
     char *base = (char *)h->granger_scratch.p;
     double *Zt = (double *)(base + o_z), *cs = (double *)(base + o_cs);
     int32_t *bits = (int32_t *)(base + o_bits), *list = (int32_t *)(base + o_list);
@@ -526,20 +481,18 @@ extern "C" int pcg_granger(pcg_handle *h, const double *X, int64_t T, int64_t n,
     hipLaunchKernelGGL(k_granger_pairs, dim3((unsigned)n, gy), dim3(GR_BLOCK), 0, h->stream, (const double *)Zt, T, (int)n,
                        maxlag, (const double *)cs, (const int32_t *)bits, out, list, ctr);
     PCG_HIP(h, hipGetLastError());
-    unsigned int marked = 0;
-    PCG_HIP(h, hipMemcpyAsync(&marked, ctr, 4, hipMemcpyDeviceToHost, h->stream));
-    PCG_HIP(h, hipStreamSynchronize(h->stream));
-    if (marked > (unsigned int)items) return pcg_fail(h, PCG_ERR_HIP, "pcg_granger: exact list overran (%u)", marked);
+    int64_t marked = 0;
+    if (int rc = pcg_read_counter(h, "pcg_granger", ctr, items, &marked)) return rc;
     if (marked) {
         const int64_t slot = 7 * T;            // doubles per block: M <= 7 columns of nobs < T rows
-        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>({(int64_t)marked, 2048, GR_WS_BYTES / (slot * 8)}));
+        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>({marked, 2048, GR_WS_BYTES / (slot * 8)}));
         if (!pcg_ensure(h, h->granger_work, (size_t)(blocks * slot * 8)))
             return pcg_fail(h, PCG_ERR_OOM, "pcg_granger: exact workspace (%lld B)", (long long)(blocks * slot * 8));
         hipLaunchKernelGGL(k_granger_exact, dim3((unsigned)blocks), dim3(GR_BLOCK), 0, h->stream, (const double *)Zt, T,
-                           (int)n, maxlag, (const int32_t *)list, (int64_t)marked, (double *)h->granger_work.p, slot, out);
+                           (int)n, maxlag, (const int32_t *)list, marked, (double *)h->granger_work.p, slot, out);
         PCG_HIP(h, hipGetLastError());
         PCG_HIP(h, hipStreamSynchronize(h->stream));
     }
-    if (exact_items) *exact_items = (int64_t)marked;
+    if (exact_items) *exact_items = marked;
     return PCG_OK;
 }

@@ -290,3 +290,28 @@ bool pcg_ensure_pinned(pcg_handle *h, PinBuf &b, size_t bytes);   // grow-only, 
             return pcg_fail((h), PCG_ERR_HIP, "%s failed: %s (%s:%d)", #expr,               \
                             hipGetErrorString(_e), __FILE__, __LINE__);                     \
     } while (0)
+
+// One scratch allocation carved into 256-byte-aligned pieces: take() each piece's offset in turn,
+// then pcg_ensure() the buffer with `total` bytes
+struct Carve {
+    size_t total = 0;
+    size_t take(size_t bytes) {
+        const size_t o = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
+
+// The hand-over to an engine's exact path: copy a device counter (unsigned int or unsigned long
+// long) to the host on h->stream, wait for the stream, and refuse a count above the capacity of
+// the list it indexes. who: the entry point, for the message
+template <class C>
+int pcg_read_counter(pcg_handle *h, const char *who, const C *dev, int64_t cap, int64_t *count) {
+    C v = 0;
+    PCG_HIP(h, hipMemcpyAsync(&v, dev, sizeof(C), hipMemcpyDeviceToHost, h->stream));
+    PCG_HIP(h, hipStreamSynchronize(h->stream));
+    if (v > (unsigned long long)cap)
+        return pcg_fail(h, PCG_ERR_HIP, "%s: exact list overran (%llu)", who, (unsigned long long)v);
+    *count = (int64_t)v;
+    return PCG_OK;
+}

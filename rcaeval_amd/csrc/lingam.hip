@@ -27,6 +27,7 @@
 #include <climits>
 #include <cmath>
 
+#include "dense_dev.h"
 #include "handle.h"
 
 // the reference rounds a * b and the following sum separately; sums that are fused say fma()
@@ -39,30 +40,6 @@ constexpr int LG_WAVES = LG_BLOCK / 64;
 constexpr int LG_CHUNK = 2048;            // rows of z_i staged in LDS at a time
 constexpr int LG_CS = 4;                  // doubles of column statistics: H(z), mean(z), var(z), unused
 constexpr int64_t LG_MAX_N = 4096;
-
-__device__ inline double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum of K per-thread values over the block (as granger.hip's); red: K * LG_WAVES
-template <int K>
-__device__ inline void block_sum(double (&v)[K], double *red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) red[k * LG_WAVES + wave] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double s = 0.0;
-        for (int w = 0; w < LG_WAVES; ++w) s += red[k * LG_WAVES + w];
-        v[k] = s;
-    }
-    __syncthreads();
-}
 
 // H(u) from mean(log(cosh(u))) and mean(u * exp(-u^2 / 2)), in the reference's operation order
 __device__ inline double lg_entropy(double mlc, double mge) {
@@ -133,7 +110,7 @@ __global__ __launch_bounds__(LG_BLOCK) void k_lingam_cols(const double *X, int64
             s[0] += a[t];
             s[1] += b[t];
         }
-        block_sum<2>(s, red);
+        block_sum<LG_BLOCK>(s, red);
         const double ma = s[0] / dT, mb = s[1] / dT;
         double q[2] = {0.0, 0.0};
         for (int64_t t = tid; t < T; t += LG_BLOCK) {
@@ -141,7 +118,7 @@ __global__ __launch_bounds__(LG_BLOCK) void k_lingam_cols(const double *X, int64
             q[0] = fma(da, db, q[0]);
             q[1] = fma(db, db, q[1]);
         }
-        block_sum<2>(q, red);
+        block_sum<LG_BLOCK>(q, red);
         // np.cov(a, b)[0, 1] / np.var(b): ddof 1 over ddof 0, r * T / (T - 1) and not r
         const double coef = (q[0] * (1.0 / (double)(T - 1))) / (q[1] / dT);
         for (int64_t t = tid; t < T; t += LG_BLOCK) {
@@ -160,14 +137,14 @@ __global__ __launch_bounds__(LG_BLOCK) void k_lingam_cols(const double *X, int64
     if (tid == 0) Ucur[p] = col;
     const double *w = W + (int64_t)col * T;
     double *z = Z + (int64_t)p * T;
-    block_sum<1>(s1, red);
+    block_sum<LG_BLOCK>(s1, red);
     const double mean = s1[0] / dT;
     double s2[1] = {0.0};
     for (int64_t t = tid; t < T; t += LG_BLOCK) {
         const double d = w[t] - mean;
         s2[0] = fma(d, d, s2[0]);
     }
-    block_sum<1>(s2, red);
+    block_sum<LG_BLOCK>(s2, red);
     const double sd = sqrt(s2[0] / dT);
     double zs[1] = {0.0};
     for (int64_t t = tid; t < T; t += LG_BLOCK) {
@@ -175,7 +152,7 @@ __global__ __launch_bounds__(LG_BLOCK) void k_lingam_cols(const double *X, int64
         z[t] = v;
         zs[0] += v;
     }
-    block_sum<1>(zs, red);
+    block_sum<LG_BLOCK>(zs, red);
     const double zmean = zs[0] / dT;
     double h[3] = {0.0, 0.0, 0.0};
     for (int64_t t = tid; t < T; t += LG_BLOCK) {
@@ -184,7 +161,7 @@ __global__ __launch_bounds__(LG_BLOCK) void k_lingam_cols(const double *X, int64
         h[1] += log(cosh(u));
         h[2] += u * exp(-(u * u) / 2.0);
     }
-    block_sum<3>(h, red);
+    block_sum<LG_BLOCK>(h, red);
     if (tid == 0) {
         double *c = cs + (int64_t)p * LG_CS;
         c[0] = lg_entropy(h[1] / dT, h[2] / dT);
@@ -338,15 +315,16 @@ int lg_check(pcg_handle *h, const char *who, const double *X, int64_t T, int64_t
 int lg_scratch(pcg_handle *h, const char *who, int64_t T, int64_t n, bool want_d, LgScratch &s) {
     const size_t col_bytes = (size_t)n * (size_t)T * 8;
     // small: column statistics | M | the two U lists
-    const size_t o_m = (size_t)n * LG_CS * 8, o_u = o_m + (size_t)n * 8, small = o_u + 2 * (size_t)n * 4;
+    Carve cv;
+    const size_t o_cs = cv.take((size_t)n * LG_CS * 8), o_m = cv.take((size_t)n * 8), o_u = cv.take(2 * (size_t)n * 4);
     if (!pcg_ensure(h, h->lingam_w, col_bytes) || !pcg_ensure(h, h->lingam_z, col_bytes) ||
-        (want_d && !pcg_ensure(h, h->lingam_d, (size_t)n * n * 8)) || !pcg_ensure(h, h->lingam_small, small))
-        return pcg_fail(h, PCG_ERR_OOM, "%s: scratch (%lld B)", who, (long long)(2 * col_bytes + (size_t)n * n * 8 + small));
+        (want_d && !pcg_ensure(h, h->lingam_d, (size_t)n * n * 8)) || !pcg_ensure(h, h->lingam_small, cv.total))
+        return pcg_fail(h, PCG_ERR_OOM, "%s: scratch (%lld B)", who, (long long)(2 * col_bytes + (size_t)n * n * 8 + cv.total));
     char *base = (char *)h->lingam_small.p;
     s.W = (double *)h->lingam_w.p;
     s.Z = (double *)h->lingam_z.p;
     s.D = (double *)h->lingam_d.p;
-    s.cs = (double *)base;
+    s.cs = (double *)(base + o_cs);
     s.M = (double *)(base + o_m);
     s.U[0] = (int32_t *)(base + o_u);
     s.U[1] = s.U[0] + n;

@@ -20,11 +20,14 @@
 //   k_pm_mci      one wave per (i, j, tau): builds Z, factorises R[Z + x + y] in LDS.
 //   k_pm_mci_exact / pm_exact_item  the exact path: Householder QR on the standardized lagged
 //                 columns themselves, one block per item; PC1 calls it inside its level loop.
+// The block sums, the column classification, the Cholesky of the fast path (chol_eliminate) and the
+// QR of the exact path (qr_eliminate) are dense_dev.h's, shared with fges.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 
+#include "dense_dev.h"
 #include "handle.h"
 
 namespace {
@@ -42,25 +45,6 @@ constexpr double PM_TAU = 1e-2;
 constexpr double PM_BETA_C = 400.0;
 constexpr int64_t PM_WS_BYTES = (int64_t)1 << 30;    // exact path: design workspace bound
 
-__device__ inline double pm_wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the block's NT threads; every thread gets the total. red: NT / 64 doubles of LDS
-template <int NT>
-__device__ inline double pm_block_sum(double v, double *red) {
-    v = pm_wave_sum(v);
-    if (NT == 64) return v;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int w = 0; w < NT / 64; ++w) s += red[w];
-    __syncthreads();
-    return s;
-}
-
 __global__ __launch_bounds__(PM_BLOCK) void k_pm_flags(const double *X, int64_t Teff, int n, int64_t ldx, int tau_max,
                                                        int32_t *flags) {
     __shared__ double red[3 * (PM_BLOCK / 64)];
@@ -75,26 +59,8 @@ __global__ __launch_bounds__(PM_BLOCK) void k_pm_flags(const double *X, int64_t 
         } else
             bad = 1.0;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = fmin(lo, __shfl_xor(lo, o, 64));
-        hi = fmax(hi, __shfl_xor(hi, o, 64));
-        bad = fmax(bad, __shfl_xor(bad, o, 64));
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[wave * 3] = lo;
-        red[wave * 3 + 1] = hi;
-        red[wave * 3 + 2] = bad;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < PM_BLOCK / 64; ++w) {
-            lo = fmin(lo, red[w * 3]);
-            hi = fmax(hi, red[w * 3 + 1]);
-            bad = fmax(bad, red[w * 3 + 2]);
-        }
-        flags[c] = bad > 0.0 ? 2 : (lo == hi ? 1 : 0);
-    }
+    const int fl = column_class<PM_BLOCK>(lo, hi, bad, red);
+    if (threadIdx.x == 0) flags[c] = fl;
 }
 
 __global__ __launch_bounds__(PM_BLOCK) void k_pm_expand(const double *X, int64_t Teff, int n, int64_t ldx, int tau_max,
@@ -108,43 +74,8 @@ __global__ __launch_bounds__(PM_BLOCK) void k_pm_expand(const double *X, int64_t
     }
 }
 
-// Gather the lower triangle of R[cols, cols] (m x m, unit diagonal) into A and eliminate its first d
-// columns (right-looking Cholesky). On return rows >= d hold, in columns < d, their rows of the
-// factor, and in columns >= d the Schur complement given cols[0..d). False (block-uniform) when a
-// pivot is below PM_TAU. Starts with a barrier: A and cols may have just been written / read.
-template <int NT>
-__device__ bool pm_factor(const double *R, int64_t W, const int *cols, int m, int d, double *A) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    for (int idx = tid; idx < m * m; idx += NT) {
-        const int r = idx / m, c = idx % m;
-        if (c <= r) A[r * PM_LD + c] = r == c ? 1.0 : R[(int64_t)cols[r] * W + cols[c]];
-    }
-    bool ok = true;
-    for (int k = 0; k < d; ++k) {
-        __syncthreads();
-        const double piv = A[k * PM_LD + k];
-        if (!(piv >= PM_TAU)) {                // block-uniform
-            ok = false;
-            break;
-        }
-        const double lkk = sqrt(piv), ik = 1.0 / lkk;
-        __syncthreads();                       // everyone has read the pivot
-        for (int r = k + 1 + tid; r < m; r += NT) A[r * PM_LD + k] *= ik;
-        if (tid == 0) A[k * PM_LD + k] = lkk;
-        __syncthreads();
-        const int w = m - k - 1;
-        for (int idx = tid; idx < w * w; idx += NT) {
-            const int r = k + 1 + idx / w, c = k + 1 + idx % w;
-            if (c <= r) A[r * PM_LD + c] -= A[r * PM_LD + k] * A[c * PM_LD + k];
-        }
-    }
-    __syncthreads();
-    return ok;
-}
-
 // |g|_1 of g = L11^-T b, the regression coefficients on Z of the variable whose factor row is b
-// (one thread; gg: d doubles of scratch)
+// (one thread; gg: d doubles of scratch). Not shared with fges.hip's one-wave form: another launch shape.
 __device__ inline double pm_coef_norm1(const double *A, const double *b, int d, double *gg) {
     double n1 = 0.0;
     for (int k = d - 1; k >= 0; --k) {
@@ -159,7 +90,7 @@ __device__ inline double pm_coef_norm1(const double *A, const double *b, int d, 
 // One test on the fast path: cols = [Z (d), x, y]. g: 130 doubles of LDS. False when a guard refuses.
 template <int NT>
 __device__ bool pm_fast_item(const double *R, int64_t W, const int *cols, int d, double *A, double *g, double &val) {
-    if (!pm_factor<NT>(R, W, cols, d + 2, d, A)) return false;
+    if (!chol_eliminate<NT, PM_LD>(R, W, cols, d + 2, d, A, PM_TAU)) return false;
     const double sxx = A[d * PM_LD + d], sxy = A[(d + 1) * PM_LD + d], syy = A[(d + 1) * PM_LD + d + 1];
     const int tid = threadIdx.x;
     if (tid < 2) g[128 + tid] = pm_coef_norm1(A, A + (d + tid) * PM_LD, d, g + tid * 64);
@@ -172,10 +103,9 @@ __device__ bool pm_fast_item(const double *R, int64_t W, const int *cols, int d,
 }
 
 // One test on the exact path: the columns cols = [Z (d), x, y] of E standardized (ddof 0) into the
-// block's workspace Aw (column-major, m x Teff), Householder QR over the Z columns with block-wide
-// reductions (a column whose remaining norm is below lstsq's rank tolerance is skipped, which is
-// the minimum-norm least-squares residual), val = the cosine of the two residuals. Each thread owns
-// the rows r = tid, tid + NT, .. for the whole factorisation.
+// block's workspace Aw (column-major, m x Teff), Householder QR over the Z columns (dense_dev.h's
+// qr_eliminate: a dependent column is skipped), val = the cosine of the two residuals. Each thread
+// owns the rows r = tid, tid + NT, .. throughout.
 template <int NT>
 __device__ double pm_exact_item(const double *E, int64_t Teff, int64_t W, const int *cols, int d, double *Aw,
                                 double *red) {
@@ -186,41 +116,17 @@ __device__ double pm_exact_item(const double *E, int64_t Teff, int64_t W, const 
         double *au = Aw + (int64_t)u * Teff;
         double s = 0.0;
         for (int64_t r = tid; r < Teff; r += NT) s += e[r * W];
-        const double mu = pm_block_sum<NT>(s, red) / (double)Teff;
+        const double mu = block_sum<NT>(s, red) / (double)Teff;
         double q = 0.0;
         for (int64_t r = tid; r < Teff; r += NT) {
             const double v = e[r * W] - mu;
             q = fma(v, v, q);
         }
-        const double isd = 1.0 / sqrt(pm_block_sum<NT>(q, red) / (double)Teff);
+        const double isd = 1.0 / sqrt(block_sum<NT>(q, red) / (double)Teff);
         for (int64_t r = tid; r < Teff; r += NT) au[r] = (e[r * W] - mu) * isd;
     }
     const double tol = (double)std::max<int64_t>(Teff, m) * 2.220446049250313e-16;
-    int64_t rdone = 0;
-    for (int k = 0; k < d; ++k) {
-        const double *ak = Aw + (int64_t)k * Teff;
-        double n0 = 0.0, n1 = 0.0;
-        for (int64_t r = tid; r < Teff; r += NT)
-            if (r >= rdone) {
-                const double v = ak[r];
-                n0 = fma(v, v, n0);
-                if (r == rdone) n1 = v;
-            }
-        n0 = pm_block_sum<NT>(n0, red);
-        n1 = pm_block_sum<NT>(n1, red);
-        if (!(n0 > tol * tol * (double)Teff)) continue;        // block-uniform: dependent column
-        const double alpha = -copysign(sqrt(n0), n1), vr = n1 - alpha, vn2 = 2.0 * (n0 - n1 * alpha);
-        for (int u = k + 1; u < m; ++u) {
-            double *au = Aw + (int64_t)u * Teff;
-            double dot = 0.0;
-            for (int64_t r = tid; r < Teff; r += NT)
-                if (r >= rdone) dot = fma(r == rdone ? vr : ak[r], au[r], dot);
-            const double f = 2.0 * pm_block_sum<NT>(dot, red) / vn2;
-            for (int64_t r = tid; r < Teff; r += NT)
-                if (r >= rdone) au[r] -= f * (r == rdone ? vr : ak[r]);
-        }
-        ++rdone;
-    }
+    const int64_t rdone = qr_eliminate<NT>(Aw, Teff, m, 0, d, 0, tol, red);
     const double *ax = Aw + (int64_t)d * Teff, *ay = Aw + (int64_t)(d + 1) * Teff;
     double sxx = 0.0, sxy = 0.0, syy = 0.0;
     for (int64_t r = tid; r < Teff; r += NT)
@@ -229,9 +135,9 @@ __device__ double pm_exact_item(const double *E, int64_t Teff, int64_t W, const 
             sxy = fma(ax[r], ay[r], sxy);
             syy = fma(ay[r], ay[r], syy);
         }
-    sxx = pm_block_sum<NT>(sxx, red);
-    sxy = pm_block_sum<NT>(sxy, red);
-    syy = pm_block_sum<NT>(syy, red);
+    sxx = block_sum<NT>(sxx, red);
+    sxy = block_sum<NT>(sxy, red);
+    syy = block_sum<NT>(syy, red);
     return sxy / sqrt(sxx * syy);
 }
 
@@ -310,10 +216,11 @@ __global__ __launch_bounds__(PM_BLOCK) void k_pm_parents(const double *R, const 
             }
         }
         // candidates outside it: one factorisation of R[top d + y], two triangular solves each
+        // (thread-serial in b[]; fges.hip's solves take a lane per row, so they are not shared)
         __syncthreads();
         if (tid < d) cols[tid] = id[tid];
         if (tid == 0) cols[d] = y;
-        bool shared_ok = pm_factor<PM_BLOCK>(R, W, cols, d + 1, d, A);
+        bool shared_ok = chol_eliminate<PM_BLOCK, PM_LD>(R, W, cols, d + 1, d, A, PM_TAU);
         const double syy = shared_ok ? A[d * PM_LD + d] : 0.0;
         if (shared_ok && tid == 0) g[128] = pm_coef_norm1(A, A + d * PM_LD, d, g);
         __syncthreads();
@@ -550,10 +457,12 @@ struct PmSmall {
 };
 bool pm_small(pcg_handle *h, int64_t n, int tau_max, PmSmall &s) {
     const int64_t W = n * (2 * tau_max + 1), items = n * n * (tau_max + 1);
-    const size_t o_crit = ((size_t)W * 4 + 255) & ~(size_t)255, o_ctr = o_crit + 64 * 8, o_list = o_ctr + 256;
-    if (!pcg_ensure(h, h->pcmci_small, o_list + (size_t)items * 4)) return false;
+    Carve cv;
+    const size_t o_flags = cv.take((size_t)W * 4), o_crit = cv.take(64 * 8), o_ctr = cv.take(16),
+                 o_list = cv.take((size_t)items * 4);
+    if (!pcg_ensure(h, h->pcmci_small, cv.total)) return false;
     char *base = (char *)h->pcmci_small.p;
-    s.flags = (int32_t *)base;
+    s.flags = (int32_t *)(base + o_flags);
     s.crit = (double *)(base + o_crit);
     s.exact_ctr = (unsigned long long *)(base + o_ctr);
     s.list_ctr = (unsigned int *)(base + o_ctr + 8);
@@ -609,10 +518,9 @@ extern "C" int pcg_pcmci_parents(pcg_handle *h, const double *X, int64_t T, int6
                        Teff, (int)n, tau_max, (const int32_t *)s.flags, (const double *)s.crit, (double *)h->pcmci_work.p,
                        slot, out, s.exact_ctr);
     PCG_HIP(h, hipGetLastError());
-    unsigned long long ex = 0;
-    PCG_HIP(h, hipMemcpyAsync(&ex, s.exact_ctr, 8, hipMemcpyDeviceToHost, h->stream));
-    PCG_HIP(h, hipStreamSynchronize(h->stream));
-    if (exact_items) *exact_items = (int64_t)ex;
+    int64_t ex = 0;                            // a count of tests, not an index into a list: no capacity
+    if (int rc1 = pcg_read_counter(h, "pcg_pcmci_parents", s.exact_ctr, INT64_MAX, &ex)) return rc1;
+    if (exact_items) *exact_items = ex;
     h->pcmci_shape[0] = T;
     h->pcmci_shape[1] = n;
     h->pcmci_shape[2] = tau_max;
@@ -640,18 +548,16 @@ extern "C" int pcg_pcmci_mci(pcg_handle *h, int64_t T, int64_t n, int tau_max, c
     hipLaunchKernelGGL(k_pm_mci, dim3(blocks), dim3(64), 0, h->stream, (const double *)h->pcmci_r.p, (int)n, tau_max,
                        (const int32_t *)s.flags, par_ids, par_count, pcap, out, s.list, s.list_ctr);
     PCG_HIP(h, hipGetLastError());
-    unsigned int marked = 0;
-    PCG_HIP(h, hipMemcpyAsync(&marked, s.list_ctr, 4, hipMemcpyDeviceToHost, h->stream));
-    PCG_HIP(h, hipStreamSynchronize(h->stream));
-    if ((int64_t)marked > items) return pcg_fail(h, PCG_ERR_HIP, "pcg_pcmci_mci: exact list overran (%u)", marked);
+    int64_t marked = 0;
+    if (int rc = pcg_read_counter(h, "pcg_pcmci_mci", s.list_ctr, items, &marked)) return rc;
     if (marked) {
-        const int64_t eblocks = std::min<int64_t>({(int64_t)marked, n, 2048});   // pcmci_work holds n slots
+        const int64_t eblocks = std::min<int64_t>({marked, n, 2048});   // pcmci_work holds n slots
         hipLaunchKernelGGL(k_pm_mci_exact, dim3((unsigned)eblocks), dim3(PM_BLOCK), 0, h->stream,
                            (const double *)h->pcmci_e.p, Teff, (int)n, tau_max, (const int32_t *)s.flags, par_ids, par_count,
-                           pcap, (const int32_t *)s.list, (int64_t)marked, (double *)h->pcmci_work.p, slot, out);
+                           pcap, (const int32_t *)s.list, marked, (double *)h->pcmci_work.p, slot, out);
         PCG_HIP(h, hipGetLastError());
         PCG_HIP(h, hipStreamSynchronize(h->stream));
     }
-    if (exact_items) *exact_items = (int64_t)marked;
+    if (exact_items) *exact_items = marked;
     return PCG_OK;
 }

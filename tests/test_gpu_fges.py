@@ -211,6 +211,26 @@ def test_near_duplicate_column_takes_the_exact_path():
     assert (np.abs(dup["gain"] - want[2:4]) <= tol).all()
 
 
+def test_exactly_duplicated_base_column_is_skipped_on_the_exact_path():
+    """B = (0, 1) with column 1 an exact copy of column 0: the exact path's QR meets a column with no
+    remaining norm and skips it, which is the minimum-norm residual, i.e. the gain on the base (0,).
+    The restatement's unpivoted-QR solve is meaningless on the full rank-deficient base (its two
+    solves differ by 0.018 there), so the expected value and delta come from the reduced base."""
+    X = fr.gen_dag(120, 5, 0)
+    X[:, 1] = X[:, 0]
+    sc = fr.Scorer(X)
+    want = sc.gain(4, 3, (0,))
+    tol = _tol(1, sc.delta)
+    eng = _eng()
+    eng.fges_begin(X)
+    out = eng.fges_gains([(3, (0, 1), [4])])
+    err = abs(out["gain"][0] - want)
+    print(f"duplicated base column: status {out['status'].tolist()} gain {out['gain'][0]!r} want {want!r} "
+          f"|error| {err:.3e} tolerance {tol:.3e} delta {sc.delta:.2e}")
+    assert out["status"].tolist() == [3] and out["exact_items"] == 1
+    assert err <= tol
+
+
 def test_flagged_columns_give_status_1_and_2():
     X = fr.gen_dag(60, 5, 2)
     X[:, 1] = 3.25

@@ -167,6 +167,28 @@ def test_near_collinear_lags_take_the_exact_path():
         assert np.max(np.abs(np.asarray(got) - np.asarray(r["val_min"])), initial=0.0) <= tol
 
 
+def test_exactly_duplicated_column_in_z_is_skipped_on_the_exact_path():
+    """Column 1 an exact copy of column 0, both in Z: the exact path's QR meets columns with no
+    remaining norm and skips them (the minimum-norm residual), so the value is the one given the
+    reduced Z. Only the two items whose own x and y have no duplicate inside Z are defined. The
+    reference is a fresh Run: one that also evaluated the undefined items has delta ~ 0.12."""
+    T, n, tau_max = 80, 3, 2
+    X = pr.gen_var(T, n, tau_max, 3)
+    X[:, 1] = X[:, 0]
+    eng = _eng()
+    eng.pcmci_parents(X.copy(), tau_max, 0.2, check_status=False)   # leaves R in the handle
+    out = eng.pcmci_mci(T, n, tau_max, [[], [], [(0, -1), (1, -1)]])
+    run = pr.Run(X, tau_max)
+    want = [run.parcorr((2, -1), (2, 0), [(0, -1), (0, -2)])[0], run.parcorr((2, -2), (2, 0), [(0, -1), (0, -3)])[0]]
+    tol = pmod.fast_path_bound(4) + 10.0 * run.delta
+    got = [out["val"][2, 2, 1], out["val"][2, 2, 2]]
+    err = np.abs(np.asarray(got) - np.asarray(want))
+    print(f"duplicated column: got {got!r} want {want!r} |error| {err} tolerance {tol:.3e} delta {run.delta:.2e}")
+    for tau in (1, 2):
+        assert out["status"][2, 2, tau] == 3 and out["dim"][2, 2, tau] == 4
+    assert (err <= tol).all()
+
+
 def test_constant_window_gives_status_1_and_value_error():
     X = pr.gen_var(80, 4, 2, 3)
     X[1:, 2] = 1.5                                           # constant over every window it enters, not over the frame

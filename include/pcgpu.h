@@ -155,7 +155,14 @@ int pcg_set_record_sample(pcg_handle *h, int64_t modulus, int64_t residue);
 #define PCG_TUNE_K1_SUPER_ORDER 17 /* 1: digit-path tiles in super-rows (1); 0: row-major         */
 #define PCG_TUNE_L1Z 18           /* 1: threshold-mode depth 1 grouped by conditioning node on one
                                      rank (k_level1_z, 1); 0: the neighbour-pair kernel           */
-#define PCG_TUNE_COUNT 19
+#define PCG_TUNE_K1_CRT_MIX 19    /* one-rank CRT K1 with no forced PCG_TUNE_K1_CRT_KS: 0 = one split for
+                                     every tile; 1 = cost model over two tile classes (1);
+                                     PCG_K1_CRT_MIX_FORCE(tA, ksA, ksB) = tiles [0, tA) in ksA slabs,
+                                     the rest in ksB (nearest achievable counts)                   */
+#define PCG_K1_CRT_MIX_FORCED (1ll << 30)
+#define PCG_K1_CRT_MIX_FORCE(tA, ksA, ksB) \
+    (PCG_K1_CRT_MIX_FORCED | ((int64_t)(tA) << 10) | ((int64_t)(ksA) << 5) | (int64_t)(ksB))
+#define PCG_TUNE_COUNT 20
 int pcg_set_tuning(pcg_handle *h, int key, int64_t value);
 int pcg_get_tuning(pcg_handle *h, int key, int64_t *value);
 
@@ -182,6 +189,11 @@ int pcg_corr_shard_bytes(pcg_handle *h, int64_t n, int64_t N, int world, int64_t
  * bits, split-K and unit count): ranks compare it before exchanging shards. h may be NULL
  * (built-in defaults), also for pcg_corr_shard_bytes.                                      */
 int pcg_k1_plan_signature(pcg_handle *h, int64_t n, int64_t N, int64_t *signature);
+/* The split-K plan a one-rank pcg_corr of (n, N) runs under this handle's knobs (h may be NULL):
+ * plan[0..7] = tiles, moduli, tA, ksA, kbA, ksB, kbB, units — tiles [0, tA) as ksA slabs of kbA
+ * k-blocks (32 rows each), the rest as ksB slabs of kbB; tA = tiles is a uniform plan. All zero
+ * when (n, N) does not take the CRT path. Host only.                                        */
+int pcg_k1_crt_plan(pcg_handle *h, int64_t n, int64_t N, int64_t *plan);
 int pcg_corr_shard_rows(int64_t n, int world, int64_t *rows_per_rank);
 int pcg_corr_shard(pcg_handle *h, const double *X, int64_t N, int64_t n, int64_t ldx, int rank,
                    int world, double *packed);

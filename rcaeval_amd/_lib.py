@@ -45,8 +45,14 @@ TUNE_KEYS = {
     "SMALL": 0, "SMALL_QCAP": 1, "LDS_DEEP": 2, "LDS_SPILL_MIN": 3, "WAVE_LO": 4, "SCREEN_MASK": 5,
     "NODE_BLOCKS": 6, "EXPORT_INLINE": 7, "NB": 8, "NBW": 9, "HOST_TRACE": 10, "K1_I8": 11, "K1_CRT": 12,
     "K1_CRT_MINN": 13, "K1_CRT_BITS": 14, "K1_CRT_KS": 15, "K1_I8_KS": 16, "K1_SUPER_ORDER": 17,
-    "L1Z": 18,
+    "L1Z": 18, "K1_CRT_MIX": 19,
 }
+
+
+def k1_crt_mix_force(tA: int, ksA: int, ksB: int) -> int:
+    """The K1_CRT_MIX value that forces tiles [0, tA) into ksA slabs and the rest into ksB
+    (PCG_K1_CRT_MIX_FORCE of include/pcgpu.h)."""
+    return (1 << 30) | (int(tA) << 10) | (int(ksA) << 5) | int(ksB)
 
 I64 = ctypes.c_int64
 I32 = ctypes.c_int32
@@ -119,6 +125,7 @@ SIGNATURES = [
     ("pcg_set_tuning", I32, [P, ctypes.c_int, I64]),
     ("pcg_get_tuning", I32, [P, ctypes.c_int, ctypes.POINTER(I64)]),
     ("pcg_k1_plan_signature", I32, [P, I64, I64, ctypes.POINTER(I64)]),
+    ("pcg_k1_crt_plan", I32, [P, I64, I64, ctypes.POINTER(I64)]),
     ("pcg_corr", I32, [P, P, I64, I64, I64, P, I64]),
     ("pcg_corr_shard_rows", I32, [I64, ctypes.c_int, ctypes.POINTER(I64)]),
     ("pcg_corr_shard_bytes", I32, [P, I64, I64, ctypes.c_int, ctypes.POINTER(I64)]),

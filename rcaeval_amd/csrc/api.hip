@@ -102,6 +102,7 @@ const TuneSpec kTune[PCG_TUNE_COUNT] = {
     {"PCG_K1_I8_KS", 0, 0, 256},
     {"PCG_K1_SUPER_ORDER", 1, 0, 1},
     {"PCG_L1Z", 1, 0, 1},
+    {"PCG_K1_CRT_MIX", 1, 0, INT32_MAX},
 };
 }  // namespace
 

@@ -537,6 +537,26 @@ struct CrtTab {
     uint32_t M[2 * CRT_L];
 };
 
+// the split-K classes of a plan: tiles [0, tA) run as ksA slabs of kbA k-blocks, tiles
+// [tA, ntiles) as ksB slabs of kbB (slab partials are exact residues that the finish sums per tile,
+// so tiles need not share one split). Units are modulus-major inside each class, class A first:
+// (mi ksA + s) tA + t, then nA + (mi ksB + s)(ntiles - tA) + (t - tA). The uniform plan is
+// tA = ntiles (class B empty): the numbering every rank and world size shares.
+struct CrtSplit {
+    int tA, ksA, kbA, ksB, kbB;
+    int64_t nA;                     // class A's units, k ksA tA
+};
+
+// tile t's slab count, the unit of its (modulus 0, slab 0) and the byte stride to the next
+// (modulus, slab) of the same tile (block-uniform wherever a block works on one tile)
+__device__ __forceinline__ void crt_tile_units(const CrtSplit &sp, int ntiles, int t, int &ks, int64_t &base,
+                                               int64_t &ustride) {
+    const bool inA = t < sp.tA;
+    ks = inA ? sp.ksA : sp.ksB;
+    base = inA ? (int64_t)t : sp.nA + (t - sp.tA);
+    ustride = (int64_t)(inA ? sp.tA : ntiles - sp.tA) * CRT_UNIT;
+}
+
 // the CRT sum of one entry: S = sum_i z_i M_i in 16-bit limb accumulators (z_i < 256, limbs
 // < 2^16: full-rate 24-bit multiply-adds, sums < 24 x 2^24), fs = sum_i z_i / m_i
 // (L = tab.L 32-bit limbs, a template parameter: no per-limb branches)
@@ -713,22 +733,33 @@ __global__ __launch_bounds__(256) void k_residues(const double *X, int64_t N, in
 
 // the residue GEMM of one 256 x 256 upper tile, one modulus and one split-K slab. 8 waves as 2 x 4,
 // each 128 x 64 (4 x 2 v_mfma_i32_32x32x32_i8 tiles, 128 accumulators); one k-block per phase
-// from an 8-slot LDS ring (6 k-blocks in flight). Units u = (mi * ks + slab) * ntiles + tile (modulus-major: a modulus group is
-// one contiguous run), this launch runs u0 .. u0 + nu - 1
+// from an 8-slot LDS ring (6 k-blocks in flight). Units in CrtSplit's numbering (modulus-major inside a class: a
+// modulus group is one contiguous run; the uniform plan's u = (mi * ks + slab) * ntiles + tile), this launch runs u0 .. u0 + nu - 1
 // (a rank's share) and writes unit u0 + l at out + l * CRT_UNIT, in lane order:
 // byte ((w * 4 + a) * 2 + b) * 1024 + lane * 16 + kk = accumulator kk of MFMA tile (a, b) of wave w.
-__global__ __launch_bounds__(512, 1) void k_xtx_crt(const int8_t *R, int TB, int64_t plane, int T, int ntiles, int ks,
-                                                  int kb, CrtTab tab, int64_t u0, int64_t nu, uint8_t *out) {
+// The grid is class A's blocks (gA, a multiple of 8, for this launch's nuA class-A units) then class
+// B's: blocks are dispatched in order, so the class put first starts first, and each class is dealt
+// to the 8 XCDs on its own (every XCD gets an eighth of the long units and an eighth of the short).
+__global__ __launch_bounds__(512, 1) void k_xtx_crt(const int8_t *R, int TB, int64_t plane, int T, int ntiles,
+                                                  CrtSplit sp, CrtTab tab, int64_t u0, int64_t nu, int64_t nuA,
+                                                  unsigned gA, uint8_t *out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int64_t lin = blockIdx.x;
+    int64_t lin;
     {   // XCD-contiguous runs: an XCD's resident blocks share the modulus and slab (all panels in its L2)
-        const int64_t per = gridDim.x / 8;
-        lin = (blockIdx.x % 8) * per + blockIdx.x / 8;
-        if (lin >= nu) return;
+        const bool blkA = blockIdx.x < gA;
+        const unsigned b = blkA ? blockIdx.x : blockIdx.x - gA;      // (gA % 8 == 0: the same XCD)
+        const int64_t per = (blkA ? gA : gridDim.x - gA) / 8;
+        lin = (b % 8) * per + b / 8;
+        if (lin >= (blkA ? nuA : nu - nuA)) return;
+        if (!blkA) lin += nuA;
     }
     const int64_t u = u0 + lin;
-    const int t = (int)(u % ntiles);
-    const int64_t sm = u / ntiles;
+    const bool inA = u < sp.nA;
+    const int64_t v = inA ? u : u - sp.nA;
+    const int tc = inA ? sp.tA : ntiles - sp.tA;
+    const int ks = inA ? sp.ksA : sp.ksB, kb = inA ? sp.kbA : sp.kbB;
+    const int t = (int)(v % tc) + (inA ? 0 : sp.tA);
+    const int64_t sm = v / tc;
     const int mi = (int)(sm / ks), slab = (int)(sm % ks);
     int bi, bj;
     tile_of(t, T, bi, bj);
@@ -868,11 +899,11 @@ __device__ __forceinline__ int crt_unit_offset(int li, int lj) {
 // sd_i = sqrt(G_ii / (N - 1)) from the diagonal entries' residues (one thread per i; every
 // residue load issued before the first use)
 template <int L>
-__global__ __launch_bounds__(256) void k_crt_diag(const uint8_t *Rs, int T, int ntiles, int ks, CrtTab tab,
+__global__ __launch_bounds__(256) void k_crt_diag(const uint8_t *Rs, int T, int ntiles, CrtSplit sp, CrtTab tab,
                                                  const int *expo, int n, double scale, double *sd) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const int bi = i / CRT_T;
+    const int bi = blockIdx.x;                         // (launched with CRT_T threads: i / CRT_T, block-uniform)
     const int t = bi * T - bi * (bi - 1) / 2;          // tile (bi, bi), row-major upper triangle
     const int ei = expo[i];
     if (ei == K1_NONFINITE) {
@@ -880,8 +911,10 @@ __global__ __launch_bounds__(256) void k_crt_diag(const uint8_t *Rs, int T, int 
         return;
     }
     const int k = tab.k;
-    const int64_t ustride = (int64_t)ntiles * CRT_UNIT;
-    const uint8_t *src = Rs + (int64_t)t * CRT_UNIT + crt_unit_offset(i % CRT_T, i % CRT_T);
+    int ks;
+    int64_t ubase, ustride;
+    crt_tile_units(sp, ntiles, t, ks, ubase, ustride);
+    const uint8_t *src = Rs + ubase * CRT_UNIT + crt_unit_offset(i % CRT_T, i % CRT_T);
     uint32_t sv[CRT_KMAX];
 #pragma unroll
     for (int mi = 0; mi < CRT_KMAX; ++mi) sv[mi] = 0;
@@ -905,11 +938,12 @@ __global__ __launch_bounds__(256) void k_crt_diag(const uint8_t *Rs, int T, int 
 // the ks slabs in u16 lanes, moduli outermost (each modulus' constants read once, 4 independent
 // chains); writes C_ij and its mirror C_ji, each in numpy's division order
 template <int L>
-__global__ __launch_bounds__(256) void k_crt_finish(const uint8_t *Rs, int T, int ntiles, int ks, CrtTab tab,
+__global__ __launch_bounds__(256) void k_crt_finish(const uint8_t *Rs, int T, int ntiles, CrtSplit sp, CrtTab tab,
                                                    const int *expo, int n, const double *sd, double scale, double *C,
                                                    int64_t ldc) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int t = (int)(gid >> 14), rem = (int)((gid >> 2) & 4095), g = (int)(gid & 3);
+    const int rem = (int)((gid >> 2) & 4095), g = (int)(gid & 3);
+    const int t = (int)(blockIdx.x >> 6);       // (256 threads: gid >> 14, block-uniform, so the slab loop is scalar)
     if (t >= ntiles) return;
     int bi, bj;
     tile_of(t, T, bi, bj);
@@ -923,8 +957,10 @@ __global__ __launch_bounds__(256) void k_crt_finish(const uint8_t *Rs, int T, in
     if (j >= n || ibase > j) return;
     const int k = tab.k;
     const int ej = expo[j];
-    const int64_t ustride = (int64_t)ntiles * CRT_UNIT;          // next (modulus, slab)
-    const uint8_t *src = Rs + (int64_t)t * CRT_UNIT + rem * 16 + 4 * g;
+    int ks;
+    int64_t ubase, ustride;                                      // ustride: next (modulus, slab)
+    crt_tile_units(sp, ntiles, t, ks, ubase, ustride);
+    const uint8_t *src = Rs + ubase * CRT_UNIT + rem * 16 + 4 * g;
     // the ks slab bytes of the 4 entries, summed in u16 lanes; every load issued before the first use
     uint32_t se[CRT_KMAX], so[CRT_KMAX];
 #pragma unroll
@@ -1002,6 +1038,7 @@ struct CrtPlan {
     CrtTab tab;
     int T = 0, ntiles = 0, ks = 0, kb = 0, TB = 0, CBp = 0;
     int64_t units = 0;
+    CrtSplit sp{};     // the two tile classes (the uniform plan: every tile in class A, ks x kb)
 };
 
 // little-endian 32-bit limb helpers for the host tables
@@ -1025,29 +1062,140 @@ static uint32_t big_div_small(const uint32_t *x, int L, uint32_t m, uint32_t *q)
 
 // the plan's knobs are the handle's (pcg_corr_sharded agrees the resulting plan's signature
 // across ranks before its all-gather, so ranks with different knobs fail together)
-static bool crt_plan_build(const int64_t *tune, int n, int64_t N, CrtPlan &p);
+static bool crt_plan_build(const int64_t *tune, int n, int64_t N, bool mixed, CrtPlan &p);
 
-// the plan is a pure function of (n, N) and five knobs; building it (modular inverses, the limb
-// tables) costs ~25 us of host time, which sat before K1's first launch on every call: one cached
-// plan per host thread
-bool crt_plan(const int64_t *tune, int n, int64_t N, CrtPlan &p) {
+// the plan is a pure function of (n, N), six knobs and `mixed`; building it (modular inverses, the
+// limb tables, the split search) costs tens of us of host time, which sat before K1's first launch on
+// every call: one cached plan per host thread and kind.
+// mixed: the caller runs every unit on one rank (pcg_corr), so the split may differ between tiles
+// (PCG_TUNE_K1_CRT_MIX); the sharded drivers, the signature and a forced PCG_TUNE_K1_CRT_KS take the
+// uniform plan, whose unit numbering every rank and world size shares
+bool crt_plan(const int64_t *tune, int n, int64_t N, CrtPlan &p, bool mixed = false) {
     struct Entry {
-        int64_t key[7];
+        int64_t key[8];
         bool ok;
         CrtPlan plan;
     };
-    thread_local Entry e{{-1, -1, -1, -1, -1, -1, -1}, false, CrtPlan{}};
-    const int64_t key[7] = {n, N, tune[PCG_TUNE_K1_I8], tune[PCG_TUNE_K1_CRT], tune[PCG_TUNE_K1_CRT_MINN],
-                            tune[PCG_TUNE_K1_CRT_BITS], tune[PCG_TUNE_K1_CRT_KS]};
+    thread_local Entry cache[2] = {{{-1, -1, -1, -1, -1, -1, -1, -1}, false, CrtPlan{}},
+                                   {{-1, -1, -1, -1, -1, -1, -1, -1}, false, CrtPlan{}}};
+    mixed = mixed && tune[PCG_TUNE_K1_CRT_KS] == 0 && tune[PCG_TUNE_K1_CRT_MIX] != 0;
+    Entry &e = cache[mixed ? 1 : 0];
+    const int64_t key[8] = {n, N, tune[PCG_TUNE_K1_I8], tune[PCG_TUNE_K1_CRT], tune[PCG_TUNE_K1_CRT_MINN],
+                            tune[PCG_TUNE_K1_CRT_BITS], tune[PCG_TUNE_K1_CRT_KS],
+                            mixed ? tune[PCG_TUNE_K1_CRT_MIX] : 0};
     if (memcmp(key, e.key, sizeof(key)) != 0) {
-        e.ok = crt_plan_build(tune, n, N, e.plan);
+        e.ok = crt_plan_build(tune, n, N, mixed, e.plan);
         memcpy(e.key, key, sizeof(key));
     }
     if (e.ok) p = e.plan;
     return e.ok;
 }
 
-static bool crt_plan_build(const int64_t *tune, int n, int64_t N, CrtPlan &p) {
+// The GEMM's time on one XCD: nA units of la us then nB units of lb us, taken in that order by P
+// one-block CUs, each CU taking the next unit when it is free. After the full rounds of long units
+// P - qA CUs are free at t0 and the qA that run the last long units at t1 = t0 + la; the short units
+// end at the smallest T = t0 + j lb or t1 + j lb by which those two groups have room for all nB.
+static double crt_makespan(int64_t nA, double la, int64_t nB, double lb, int P) {
+    if (nA == 0) return (double)((nB + P - 1) / P) * lb;
+    const int64_t rA = nA / P, qA = nA % P;
+    const double t0 = (double)rA * la, t1 = t0 + la, tl = qA ? t1 : t0;    // tl: the last long unit ends
+    if (nB == 0) return tl;
+    auto room = [&](double T) {
+        int64_t c = (P - qA) * (int64_t)std::floor((T - t0) / lb + 1e-9);
+        if (qA && T >= t1) c += qA * (int64_t)std::floor((T - t1) / lb + 1e-9);
+        return c;
+    };
+    double best = 1e300;
+    for (int f = 0; f < (qA ? 2 : 1); ++f) {
+        const double base = f ? t1 : t0;
+        int64_t lo = 0, hi = nB;                 // room(t0 + nB lb) >= nB: at least one CU is free at t0
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) / 2;
+            if (room(base + (double)mid * lb) >= nB) hi = mid;
+            else lo = mid + 1;
+        }
+        best = std::min(best, base + (double)lo * lb);
+    }
+    return std::max(best, tl);
+}
+
+// the achievable slab count nearest to `want` (a slab is a multiple of CRT_KB k-blocks), 0 if none
+static int crt_slabs(int TB, int want, int *kb) {
+    int best = 0, bd = INT32_MAX;
+    for (int ks = 1; ks <= 16; ++ks) {
+        int kbk = (TB + ks - 1) / ks;
+        kbk = (kbk + CRT_KB - 1) / CRT_KB * CRT_KB;
+        if ((TB + kbk - 1) / kbk != ks || kbk > CRT_MAXKB) continue;
+        if (std::abs(ks - want) < bd) {
+            bd = std::abs(ks - want);
+            best = ks;
+            *kb = kbk;
+        }
+    }
+    return best;
+}
+
+// The two-class split of a one-rank K1 (PCG_TUNE_K1_CRT_MIX; p holds the uniform plan, which stays
+// when no mixed plan is cheaper). One split for all tiles leaves the last round of 256 one-block CUs
+// partly empty: the headline (n 2000, N 10^4: 36 tiles x 16 moduli, 314 k-blocks) runs 1152 units
+// of 160 k-blocks as 4.5 rounds, i.e. 5. Measured there with a forced uniform split (k_xtx_crt,
+// us): ks 1: 424, 2: 391, 3: 386, 4: 409, 8: 480 = 0.41 us per k-block (the matrix cores' rate:
+// 16 MFMAs of 64 cycles per SIMD) x rounds x slab length + 12.6 us per round (ring fill, epilogue,
+// block turn-over) to within 3 % for ks <= 4. So a unit costs kb x 0.41 + 12.6 us, the GEMM is the
+// makespan of the units of one XCD (an eighth of each class, long class first) on its 32 CUs, and
+// the residue bytes cost 0.026 us per unit as in the uniform model. Predictions:
+//   n 2000: 32 tiles unsplit + 4 tiles x 4 slabs (768 units: two rounds of 316 and one of 80):
+//           330 + 20 us against the uniform ks 2's 391 + 30 (measured: k_xtx_crt 341 against 384,
+//           k_crt_diag + k_crt_finish 67 against 68)
+//   n 1000 (10 tiles x 16): 8 tiles x 2 slabs + 2 tiles x 8 (512 units: one round of 160 and one
+//           of 40): 107 + 13 us against the uniform ks 3's two rounds of 108, 114 + 12
+//   n 4000 (136 tiles x 16): 128 tiles unsplit + 8 tiles x 2 slabs (2304 units: eight rounds of
+//           316 and one of 160): 1215 + 60 us against the uniform ks 1's nine rounds, 1279 + 57
+static void crt_plan_mix(int64_t knob, CrtPlan &p) {
+    const int k = p.tab.k, nt = p.ntiles;
+    auto set = [&](int tA, int ksA, int kbA, int ksB, int kbB) {
+        if (tA == 0) { tA = nt; ksA = ksB; kbA = kbB; }           // all B = all A
+        if (tA == nt) { ksB = ksA; kbB = kbA; }
+        p.sp = CrtSplit{tA, ksA, kbA, ksB, kbB, (int64_t)k * ksA * tA};
+        p.units = p.sp.nA + (int64_t)k * ksB * (nt - tA);
+        p.ks = ksA;
+        p.kb = kbA;
+    };
+    if (knob & PCG_K1_CRT_MIX_FORCED) {        // a forced (tA, ksA, ksB): the nearest achievable counts
+        int kbA = 0, kbB = 0;
+        const int tA = (int)std::min<int64_t>((knob >> 10) & 0xfffff, nt);
+        const int ksA = crt_slabs(p.TB, (int)((knob >> 5) & 31), &kbA), ksB = crt_slabs(p.TB, (int)(knob & 31), &kbB);
+        if (ksA && ksB) set(tA, ksA, kbA, ksB, kbB);
+        return;
+    }
+    constexpr double US_KB = 0.41, US_UNIT = 12.6, US_BYTES = 0.026;
+    int ksv[16], kbv[16], nk = 0;
+    for (int ks = 1; ks <= 16; ++ks) {
+        int kb = 0;
+        if (crt_slabs(p.TB, ks, &kb) == ks) { ksv[nk] = ks; kbv[nk++] = kb; }
+    }
+    auto cost = [&](int tA, int a, int b) {
+        const int64_t nA = (int64_t)k * ksv[a] * tA, nB = (int64_t)k * ksv[b] * (nt - tA);
+        return crt_makespan((nA + 7) / 8, kbv[a] * US_KB + US_UNIT, (nB + 7) / 8, kbv[b] * US_KB + US_UNIT, 32) +
+               (double)(nA + nB) * US_BYTES;
+    };
+    double best = 1e300;
+    int bt = nt, ba = 0, bb = 0;
+    for (int a = 0; a < nk; ++a) {             // the uniform plans first: a mixed plan has to beat them
+        const double c = cost(nt, a, a);
+        if (c < best) { best = c; ba = bb = a; }
+    }
+    const int step = std::max(1, nt / 256);    // (large n: the tail is a small part, a coarse tA will do)
+    for (int tA = step; tA < nt; tA += step)
+        for (int a = 0; a < nk; ++a)
+            for (int b = a + 1; b < nk; ++b) {   // class A is the longer one (fewer slabs): it goes first
+                const double c = cost(tA, a, b);
+                if (c < best) { best = c; bt = tA; ba = a; bb = b; }
+            }
+    if (nk) set(bt, ksv[ba], kbv[ba], ksv[bb], kbv[bb]);
+}
+
+static bool crt_plan_build(const int64_t *tune, int n, int64_t N, bool mixed, CrtPlan &p) {
     if (!tune[PCG_TUNE_K1_I8] || !tune[PCG_TUNE_K1_CRT] || n < tune[PCG_TUNE_K1_CRT_MINN]) return false;
     const int bmin = (int)std::min<int64_t>(63, std::max<int64_t>(32, tune[PCG_TUNE_K1_CRT_BITS]));   // k_residues: b in [32, 63]
     // k: the fewest moduli whose product leaves b >= bmin bits per value, M > 2 N 4^b (0.01 bit margin)
@@ -1134,6 +1282,8 @@ static bool crt_plan_build(const int64_t *tune, int n, int64_t N, CrtPlan &p) {
         p.ks = (p.TB + kbk - 1) / kbk;
     }
     p.units = (int64_t)p.ntiles * k * p.ks;
+    p.sp = CrtSplit{p.ntiles, p.ks, p.kb, p.ks, p.kb, p.units};
+    if (mixed) crt_plan_mix(tune[PCG_TUNE_K1_CRT_MIX], p);
     return true;
 }
 
@@ -1153,8 +1303,10 @@ int crt_residues(pcg_handle *h, const CrtPlan &p, const double *X, int64_t N, in
 void crt_gemm(pcg_handle *h, const CrtPlan &p, const int8_t *R, int64_t u0, int64_t nu, uint8_t *out) {
     if (nu <= 0) return;
     const int64_t plane = (int64_t)p.CBp * p.TB * 2048;
-    hipLaunchKernelGGL(k_xtx_crt, dim3((unsigned)((nu + 7) / 8 * 8)), dim3(512), CRT_PR * 16384, h->stream, R,
-                       p.TB, plane, p.T, p.ntiles, p.ks, p.kb, p.tab, u0, nu, out);
+    const int64_t nuA = std::min(nu, std::max<int64_t>(p.sp.nA - u0, 0));     // this launch's class-A units
+    const unsigned gA = (unsigned)((nuA + 7) / 8 * 8), gB = (unsigned)((nu - nuA + 7) / 8 * 8);
+    hipLaunchKernelGGL(k_xtx_crt, dim3(gA + gB), dim3(512), CRT_PR * 16384, h->stream, R, p.TB, plane, p.T,
+                       p.ntiles, p.sp, p.tab, u0, nu, nuA, gA, out);
 }
 
 // C from the units' residues: the diagonal (sd) first, then every upper entry and its mirror
@@ -1164,10 +1316,10 @@ void crt_finish(pcg_handle *h, const CrtPlan &p, const uint8_t *Rs, const int *e
     const int64_t threads = (int64_t)p.ntiles * 16384;
 #define CRT_LAUNCH(L_)                                                                                       \
     do {                                                                                                     \
-        hipLaunchKernelGGL((k_crt_diag<L_>), dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, h->stream, Rs, \
-                           p.T, p.ntiles, p.ks, p.tab, expo, nn, scale, sd);                                  \
+        hipLaunchKernelGGL((k_crt_diag<L_>), dim3((unsigned)((nn + CRT_T - 1) / CRT_T)), dim3(CRT_T), 0,      \
+                           h->stream, Rs, p.T, p.ntiles, p.sp, p.tab, expo, nn, scale, sd);                   \
         hipLaunchKernelGGL((k_crt_finish<L_>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0,         \
-                           h->stream, Rs, p.T, p.ntiles, p.ks, p.tab, expo, nn, (const double *)sd, scale, C, \
+                           h->stream, Rs, p.T, p.ntiles, p.sp, p.tab, expo, nn, (const double *)sd, scale, C, \
                            ldc);                                                                              \
     } while (0)
     if (p.tab.L <= 4) { CRT_LAUNCH(4); }
@@ -1384,6 +1536,18 @@ extern "C" int pcg_k1_plan_signature(pcg_handle *h, int64_t n, int64_t N, int64_
     return PCG_OK;
 }
 
+extern "C" int pcg_k1_crt_plan(pcg_handle *h, int64_t n, int64_t N, int64_t *plan) {
+    if (n < 1 || N < 2 || n > (1 << 24) || !plan) return pcg_fail(h, PCG_ERR_INVALID, "pcg_k1_crt_plan");
+    const K1Tune t(h);
+    CrtPlan cp;
+    memset(plan, 0, 8 * sizeof(int64_t));
+    if (crt_plan(t.v, (int)n, N, cp, true)) {
+        const int64_t v[8] = {cp.ntiles, cp.tab.k, cp.sp.tA, cp.sp.ksA, cp.sp.kbA, cp.sp.ksB, cp.sp.kbB, cp.units};
+        memcpy(plan, v, sizeof(v));
+    }
+    return PCG_OK;
+}
+
 extern "C" int pcg_corr_shard_rows(int64_t n, int world, int64_t *rows_per_rank) {
     if (n < 1 || world < 1 || !rows_per_rank) return PCG_ERR_INVALID;
     const int64_t T = (n + TILE - 1) / TILE;
@@ -1597,7 +1761,7 @@ int pcg_corr_launch(pcg_handle *h, const double *X, int64_t N, int64_t n, int64_
     const int nn = (int)n;
     const double scale = 1.0 / (double)(N - 1);
     CrtPlan cp;
-    if (crt_plan(h->tune, nn, N, cp)) {
+    if (crt_plan(h->tune, nn, N, cp, true)) {          // every unit on this rank: the split may differ between tiles
         double *mean;
         int *expo = nullptr;
         int rc = column_means(h, X, N, nn, ldx, &mean, &expo);

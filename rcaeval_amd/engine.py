@@ -154,6 +154,13 @@ class Engine:
         check(self.h, self.lib.pcg_k1_plan_signature(self.h, int(n), int(N), ctypes.byref(v)), "pcg_k1_plan_signature")
         return v.value
 
+    def k1_crt_plan(self, n: int, N: int) -> dict:
+        """The split-K plan a one-rank ``corr`` of (n, N) runs under this engine's knobs
+        (pcg_k1_crt_plan); every value 0 when (n, N) does not take the CRT path."""
+        v = (ctypes.c_int64 * 8)()
+        check(self.h, self.lib.pcg_k1_crt_plan(self.h, int(n), int(N), v), "pcg_k1_crt_plan")
+        return dict(zip(("tiles", "moduli", "tA", "ksA", "kbA", "ksB", "kbB", "units"), (int(x) for x in v)))
+
     # ------------------------------------------------------------------ helpers
     def to_device(self, a) -> "object":
         torch = _torch()

@@ -655,6 +655,51 @@ int pcg_fges_gains(pcg_handle *h, int64_t n_groups, const int32_t *grp_y, const 
 /* The limits and guards the fGES kernels were built with (host-only, any may be NULL).           */
 int pcg_fges_limits(int32_t *b_cap, int32_t *max_n, int32_t *narrow_max, double *tau, double *beta_c);
 
+/* ---- column scalers (baro = robust_scaler, nsigma) -----------------------------------------
+ * Replaces the per-column sklearn fits of RCAEval/e2e/__init__.py:83-170: a scaler is fitted on
+ * each column a of the normal window A (N x n) and the column's score is the largest scaled
+ * value of the same column b of the anomalous window B (M x n), z = (b - center) / scale (one
+ * subtraction, one division), score = max z. Every output is bit for bit what numpy 2.2 /
+ * scikit-learn 1.7 compute; signed zeros are not distinguished.
+ *
+ * mode 0, RobustScaler: center = the median of a (the mean of the two middle order statistics
+ * for even N), scale = q75 - q25 with numpy's linear-interpolated percentiles (virtual index
+ * v = N p + (1 + p (1 - 1 - 1)) - 1, lo = floor v, t = v - lo, hi = min(lo + 1, N - 1),
+ * q = s[lo] + (s[hi] - s[lo]) t for t < 0.5, else s[hi] - (s[hi] - s[lo]) (1 - t)); a scale below
+ * 10 eps becomes 1. The six order statistics are selected exactly (what a full sort would put at
+ * those ranks) on order-preserving 64-bit keys of the doubles: columns of N <= lds_rows
+ * (pcg_scaler_limits) are sorted in LDS, longer ones go through an 8-bit radix select over the
+ * column in global memory whose 32-bit counters bound N by 2^31 - 1.
+ *
+ * mode 1, StandardScaler: S = sum a in numpy's order (pairwise inside
+ * blocks of 8192 elements, the blocks added in turn), center = S / N, tmp = a - S / N,
+ * var = (sum tmp^2 - (sum tmp)^2 / N) / N with the same order, scale = sqrt(var), or 1 where
+ * var <= N eps var + (N center eps)^2 (scikit-learn's _is_constant_feature).
+ *
+ * A case's pointers are device memory: A with row stride lda >= n, B with row stride ldb >= n.
+ * Its column c writes slot out_off + c of center / scale / score (device doubles) and status
+ * (device int32): 0 ok, 1 a NaN or Inf in a or b, or (mode 0) a center or scale that overflowed
+ * on finite input (the other three outputs are then unspecified).
+ * pcg_scaler_batch takes a host array of `count` cases and runs every column of every case in
+ * one launch sequence on the handle's stream, synchronised on return. A case with N < 1, M < 1,
+ * N or M > 2^31 - 1, n < 0, lda < n, ldb < n or out_off < 0, or a mode other than 0 / 1, is
+ * PCG_ERR_INVALID before anything is launched. pcg_scaler_case is the batch of one case.        */
+typedef struct {
+    const double *A;                   /* N x n normal window, row stride lda                 */
+    const double *B;                   /* M x n anomalous window, row stride ldb              */
+    int64_t N, M, n, lda, ldb;
+    int64_t out_off;                   /* first output slot of the case's columns             */
+} pcg_scaler_case_t;
+int pcg_scaler_case(pcg_handle *h, const double *A, int64_t lda, const double *B, int64_t ldb, int64_t N,
+                    int64_t M, int64_t n, int64_t out_off, int mode, double *center, double *scale,
+                    double *score, int32_t *status);
+int pcg_scaler_batch(pcg_handle *h, const pcg_scaler_case_t *cases, int64_t count, int mode, double *center,
+                     double *scale, double *score, int32_t *status);
+/* sizeof(pcg_scaler_case_t) as the library was built (host only).                              */
+int pcg_scaler_abi_info(int64_t *case_bytes);
+/* The largest N the in-LDS sort takes (host only).                                             */
+int pcg_scaler_limits(int64_t *lds_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,12 @@ class PcgCaseResult(ctypes.Structure):
                 ("stats", PcgStats), ("deg", (I32 * 64) * PCG_MAX_LEVELS)]
 
 
+class PcgScalerCase(ctypes.Structure):
+    """pcg_scaler_case_t: one case of pcg_scaler_batch (A and B device memory)."""
+    _fields_ = [("A", P), ("B", P), ("N", I64), ("M", I64), ("n", I64), ("lda", I64), ("ldb", I64),
+                ("out_off", I64)]
+
+
 # (name, restype, argtypes) — exactly the exports of include/pcgpu.h
 SIGNATURES = [
     ("pcg_abi_info", I32, [ctypes.POINTER(I64), ctypes.POINTER(I64), ctypes.POINTER(I32)]),
@@ -194,6 +200,10 @@ SIGNATURES = [
     ("pcg_fges_gains", I32, [P, I64, P, P, P, I64, P, P, I64, I64, P, P, ctypes.POINTER(I64)]),
     ("pcg_fges_limits", I32, [ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(D),
                               ctypes.POINTER(D)]),
+    ("pcg_scaler_case", I32, [P, P, I64, P, I64, I64, I64, I64, I64, ctypes.c_int, P, P, P, P]),
+    ("pcg_scaler_batch", I32, [P, ctypes.POINTER(PcgScalerCase), I64, ctypes.c_int, P, P, P, P]),
+    ("pcg_scaler_abi_info", I32, [ctypes.POINTER(I64)]),
+    ("pcg_scaler_limits", I32, [ctypes.POINTER(I64)]),
 ]
 
 _lib = None
@@ -247,6 +257,12 @@ def check_abi(lib, stats_cls=None, record_cls=None) -> None:
             f"{LIB_PATH}: ABI mismatch (library sizeof(pcg_case)={cb.value}, sizeof(pcg_case_result)={qb.value}; "
             f"bindings {ctypes.sizeof(PcgCase)}, {ctypes.sizeof(PcgCaseResult)}): rebuild the library "
             "or update rcaeval_amd/_lib.py with include/pcgpu.h")
+    sb = I64()
+    lib.pcg_scaler_abi_info(ctypes.byref(sb))
+    if sb.value != ctypes.sizeof(PcgScalerCase):
+        raise EngineUnavailable(
+            f"{LIB_PATH}: ABI mismatch (library sizeof(pcg_scaler_case_t)={sb.value}; bindings "
+            f"{ctypes.sizeof(PcgScalerCase)}): rebuild the library or update rcaeval_amd/_lib.py with include/pcgpu.h")
 
 
 class PcgError(RuntimeError):

@@ -23,6 +23,7 @@
 
 #include <algorithm>
 
+#include "dense_dev.h"
 #include "handle.h"
 
 namespace {
@@ -36,54 +37,6 @@ struct ChiPlan {
     int s[PCG_MAX_LEVEL_DEPTH];
     int64_t cum[PCG_MAX_LEVEL_DEPTH];
 };
-
-// numpy pairwise_sum over a[0..n): leaves of <= 128 (8 accumulators), halves rounded down to a
-// multiple of 8 — post-order over an explicit stack (thread-local)
-__device__ double np_pairwise_leaf(const double *a, int64_t n) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int64_t i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    double r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int64_t i = 8;
-    for (; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-}
-
-__device__ double np_pairwise_sum(const double *a, int64_t n) {
-    struct Frame { int64_t s, n; int state; double left; };
-    Frame st[64];
-    int sp = 1;
-    st[0] = {0, n, 0, 0.0};
-    double result = 0.0;      // value of the frame that finished last
-    while (sp) {
-        Frame &f = st[sp - 1];
-        if (f.n <= 128) {
-            result = np_pairwise_leaf(a + f.s, f.n);
-            --sp;
-            continue;
-        }
-        int64_t n2 = f.n / 2;
-        n2 -= n2 % 8;
-        if (f.state == 0) {
-            f.state = 1;
-            st[sp++] = {f.s, n2, 0, 0.0};
-        } else if (f.state == 1) {
-            f.left = result;
-            f.state = 2;
-            st[sp++] = {f.s + n2, f.n - n2, 0, 0.0};
-        } else {
-            result = f.left + result;
-            --sp;
-        }
-    }
-    return result;
-}
 
 __global__ __launch_bounds__(CHI_BLOCK) void k_chisq(const int32_t *data, int64_t N, int n, const int32_t *card,
                                                      const int32_t *tests, int stride, int64_t count, int g_sq,

@@ -1,5 +1,6 @@
 // dense_dev.h — the block-wide reductions and the two small dense factorisations shared by the side
-// engines (granger.hip, lingam.hip, pcmci.hip, fges.hip). Device code only; NT is the block size.
+// engines (granger.hip, lingam.hip, pcmci.hip, fges.hip), and numpy's pairwise summation order
+// (chisq.hip, scaler.hip). Device code only; NT is the block size.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -87,6 +88,72 @@ __device__ inline int column_class(double lo, double hi, double bad, double *red
         bad = fmax(bad, red[w * 3 + 2]);
     }
     return bad > 0.0 ? 2 : (lo == hi ? 1 : 0);
+}
+
+// numpy's pairwise_sum over at(0) .. at(n - 1), one thread: leaves of <= 128 elements (8
+// accumulators), halves rounded down to a multiple of 8 — post-order over an explicit stack
+// (thread-local). at(i) is element i: a pointer read, or a strided / transformed one
+template <class At>
+__device__ inline double np_pairwise_leaf(At at, int64_t s, int64_t n) {
+#pragma clang fp contract(off)      // at() may end in a product: it is rounded before it is added
+    if (n < 8) {
+        double res = 0.0;
+        for (int64_t i = 0; i < n; ++i) res += at(s + i);
+        return res;
+    }
+    double r[8];
+    for (int j = 0; j < 8; ++j) r[j] = at(s + j);
+    int64_t i = 8;
+    for (; i < n - (n % 8); i += 8)
+        for (int j = 0; j < 8; ++j) r[j] += at(s + i + j);
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res += at(s + i);
+    return res;
+}
+
+template <class At>
+__device__ inline double np_pairwise_sum_at(At at, int64_t n) {
+    struct Frame { int64_t s, n; int state; double left; };
+    Frame st[64];
+    int sp = 1;
+    st[0] = {0, n, 0, 0.0};
+    double result = 0.0;      // value of the frame that finished last
+    while (sp) {
+        Frame &f = st[sp - 1];
+        if (f.n <= 128) {
+            result = np_pairwise_leaf(at, f.s, f.n);
+            --sp;
+            continue;
+        }
+        int64_t n2 = f.n / 2;
+        n2 -= n2 % 8;
+        if (f.state == 0) {
+            f.state = 1;
+            st[sp++] = {f.s, n2, 0, 0.0};
+        } else if (f.state == 1) {
+            f.left = result;
+            f.state = 2;
+            st[sp++] = {f.s + n2, f.n - n2, 0, 0.0};
+        } else {
+            result = f.left + result;
+            --sp;
+        }
+    }
+    return result;
+}
+
+__device__ inline double np_pairwise_sum(const double *a, int64_t n) {
+    return np_pairwise_sum_at([a](int64_t i) { return a[i]; }, n);
+}
+
+// numpy's sum of n contiguous doubles: the reduction runs in buffer-sized blocks of 8192 elements,
+// pairwise inside a block, the blocks accumulated in order onto 0.0
+template <class At>
+__device__ inline double np_sum_at(At at, int64_t n) {
+    double v = 0.0;
+    for (int64_t b0 = 0; b0 < n; b0 += 8192)
+        v += np_pairwise_sum_at([=](int64_t i) { return at(b0 + i); }, n - b0 < 8192 ? n - b0 : (int64_t)8192);
+    return v;
 }
 
 // Gather the lower triangle of R[cols, cols] (m x m, unit diagonal; R has leading dimension ldr)

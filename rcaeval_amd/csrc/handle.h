@@ -94,6 +94,8 @@ struct pcg_handle {
     DevBuf fges_e, fges_r, fges_small, fges_list, fges_work;
     int64_t fges_shape[2] = {0, 0};
     bool fges_ok = false;
+    DevBuf scaler_up;               // pcg_scaler_batch: the cases and the tile lists (one H2D copy)
+    bool scaler_lds_set = false;    // k_sc_sort's dynamic-LDS limit was raised on this handle's device
     DevBuf k1_digits;               // K1 int8 digit / residue planes of the centred X (corr.hip)
     // the (N, n, k, b) a CRT-mode pcg_corr_shard computed h->colmean's column exponents for;
     // pcg_corr_shard_finish refuses to rebuild C from exponents of any other call

@@ -13,7 +13,7 @@ import time
 import numpy as np
 
 from . import _lib
-from ._lib import PcgRecord, PcgStats, check
+from ._lib import PcgRecord, PcgScalerCase, PcgStats, check
 
 _ENGINES: dict = {}
 
@@ -797,6 +797,44 @@ class Engine:
                                               ctypes.c_void_p(gain.data_ptr()), ctypes.c_void_p(st.data_ptr()),
                                               ctypes.byref(exact)), "pcg_fges_gains")
         return {"gain": gain.cpu().numpy()[:ni], "status": st.cpu().numpy()[:ni], "exact_items": int(exact.value)}
+
+    # ------------------------------------------------------------------ column scalers
+    def scaler_limits(self) -> dict:
+        """``lds_rows``: the largest N the in-LDS sort of ``scaler_scores`` takes (``pcg_scaler_limits``)."""
+        v = ctypes.c_int64()
+        check(self.h, self.lib.pcg_scaler_limits(ctypes.byref(v)), "pcg_scaler_limits")
+        return {"lds_rows": int(v.value)}
+
+    def scaler_scores(self, cases, mode) -> list:
+        """Per-column scaler fits and scores of many cases in one call (``pcg_scaler_batch``).
+        ``cases``: a list of ``(A, B)``, A the N x n normal window and B the M x n anomalous one,
+        host arrays or fp64 device tensors (a row-strided device view is read in place). ``mode``:
+        0 / "robust" (median, inter-quartile range) or 1 / "standard" (mean, standard deviation).
+        Returns per case a dict of the host arrays ``center``, ``scale``, ``score`` (float64) and
+        ``status`` (int32: 0 ok, 1 a NaN or Inf in the column, the other three then unspecified),
+        n entries each."""
+        torch = _torch()
+        mode = {"robust": 0, "standard": 1}.get(mode, mode)
+        arr = (PcgScalerCase * max(len(cases), 1))()
+        keep, offs, off = [], [], 0
+        for i, (A, B) in enumerate(cases):
+            Ad, N, n, lda = self._rows(A)
+            Bd, M, nb, ldb = self._rows(B)
+            if nb != n:
+                raise ValueError(f"scaler_scores: case {i}: A has {n} columns, B has {nb}")
+            keep.append((Ad, Bd))
+            arr[i] = PcgScalerCase(Ad.data_ptr(), Bd.data_ptr(), N, M, n, lda, ldb, off)
+            offs.append((off, off + n))
+            off += n
+        vals = torch.empty((3, max(off, 1)), dtype=torch.float64, device=self.device)
+        st = torch.empty(max(off, 1), dtype=torch.int32, device=self.device)
+        row = vals.stride(0) * 8
+        check(self.h, self.lib.pcg_scaler_batch(self.h, arr, len(cases), int(mode),
+                                                *(ctypes.c_void_p(vals.data_ptr() + k * row) for k in range(3)),
+                                                ctypes.c_void_p(st.data_ptr())), "pcg_scaler_batch")
+        v, s = vals.cpu().numpy(), st.cpu().numpy()
+        return [{"center": v[0, lo:hi], "scale": v[1, lo:hi], "score": v[2, lo:hi], "status": s[lo:hi]}
+                for lo, hi in offs]
 
     # ------------------------------------------------------------------ K4
     def pagerank_dense(self, A, damping: float = 0.85, n_iter: int = 10, tol: float = 1e-6) -> np.ndarray:

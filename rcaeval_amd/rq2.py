@@ -44,9 +44,10 @@ DATASET_MAP = {                                   # rq2.py:135-144
 
 def methods():
     """Methods this engine serves (``rq2.py:36-59`` resolves them by name)."""
-    from .e2e import (circa, cloudranger, fges_pagerank, fges_randomwalk, granger_pagerank, granger_randomwalk,
-                      micro_diag, microcause, pc_pagerank, pc_randomwalk)
-    return {"pc_pagerank": pc_pagerank, "pc_randomwalk": pc_randomwalk, "cloudranger": cloudranger,
+    from .e2e import (baro, circa, cloudranger, fges_pagerank, fges_randomwalk, granger_pagerank,
+                      granger_randomwalk, micro_diag, microcause, nsigma, pc_pagerank, pc_randomwalk, robust_scaler)
+    return {"baro": baro, "robust_scaler": robust_scaler, "nsigma": nsigma,
+            "pc_pagerank": pc_pagerank, "pc_randomwalk": pc_randomwalk, "cloudranger": cloudranger,
             "circa": circa, "granger_pagerank": granger_pagerank, "granger_randomwalk": granger_randomwalk,
             "micro_diag": micro_diag, "microcause": microcause, "fges_pagerank": fges_pagerank,
             "fges_randomwalk": fges_randomwalk}
@@ -285,18 +286,25 @@ def stop_loaders() -> None:
         _LOADERS = None
 
 
-def process_loaded_batch(cs: list, dataset: str, result_path: str) -> list:
-    """``process_loaded`` of several loaded cases with their PC runs batched
-    (``e2e.pc_pagerank_batch``); the JSON files are written in the order of ``cs``. If the batch
-    itself raises (an engine fault), the cases run one by one instead, so the files of the cases
-    before the failing one are written and the error is raised at that case's position."""
-    from .e2e import pc_pagerank_batch
+def batch_methods():
+    """The methods ``--batch`` serves, each with the entry point that runs many cases in one launch."""
+    from .e2e import baro_batch, nsigma_batch, pc_pagerank_batch
+    return {"pc_pagerank": pc_pagerank_batch, "baro": baro_batch, "robust_scaler": baro_batch,
+            "nsigma": nsigma_batch}
+
+
+def process_loaded_batch(cs: list, dataset: str, result_path: str, method: str = "pc_pagerank") -> list:
+    """``process_loaded`` of several loaded cases with their device work batched
+    (``e2e.pc_pagerank_batch``, or ``baro_batch`` / ``nsigma_batch`` for the scaler methods); the
+    JSON files are written in the order of ``cs``. If the batch itself raises (an engine fault),
+    the cases run one by one instead, so the files of the cases before the failing one are written
+    and the error is raised at that case's position."""
     t0 = time.perf_counter()
     try:
-        outs = pc_pagerank_batch([(c["data"], c["inject_time"]) for c in cs], dataset=dataset,
-                                 dk_select_useful=False)
+        outs = batch_methods()[method]([(c["data"], c["inject_time"]) for c in cs], dataset=dataset,
+                                       dk_select_useful=False)
     except Exception:      # noqa: BLE001 - repeated per case below, raised where it belongs
-        return [process_loaded(c, "pc_pagerank", dataset, result_path) for c in cs]
+        return [process_loaded(c, method, dataset, result_path) for c in cs]
     seconds = (time.perf_counter() - t0) / max(len(cs), 1)
     res = []
     for c, out in zip(cs, outs):
@@ -312,7 +320,7 @@ def process_loaded_batch(cs: list, dataset: str, result_path: str) -> list:
 
 
 def _run_batched(mine: list, dataset: str, result_path: str, batch: int, prefetch: int, loader: str,
-                 kw: dict) -> list:
+                 kw: dict, method: str = "pc_pagerank") -> list:
     """``run``'s case loop for ``batch > 0``: groups of up to ``batch`` consecutive cases of the
     sorted list, the next group loading while the current one runs. A case whose load fails
     raises after the cases before it were processed, as in the sequential loop."""
@@ -338,7 +346,7 @@ def _run_batched(mine: list, dataset: str, result_path: str, batch: int, prefetc
                     err = e
                     break
             if loaded:
-                per_case.extend(process_loaded_batch(loaded, dataset, result_path))
+                per_case.extend(process_loaded_batch(loaded, dataset, result_path, method))
             if err is not None:
                 raise err
     finally:
@@ -358,9 +366,9 @@ def run(dataset_dir: str, method: str, dataset: str, output: str = "output", len
     cases ahead of the GPU thread: threads by default (safe from any caller); ``loader="process"``
     uses spawned processes (faster — pandas' parser holds the GIL — but the caller's script needs
     an ``if __name__ == "__main__"`` guard; ``main`` and ``bench.py`` opt in, and ``main`` stops them
-    at its end). ``batch=B`` (> 0, method ``pc_pagerank`` only; 0 = the per-case loop) runs the PC of
-    up to B consecutive cases in one batched launch (``e2e.pc_pagerank_batch``); the result files
-    are still written in sorted case order."""
+    at its end). ``batch=B`` (> 0, the methods of ``batch_methods``; 0 = the per-case loop) runs the
+    device work of up to B consecutive cases in one batched launch (``e2e.pc_pagerank_batch``,
+    ``baro_batch``, ``nsigma_batch``); the result files are still written in sorted case order."""
     is_synthetic = "circa" in dataset or "rcd" in dataset
     result_path = join(output, "results")
     os.makedirs(result_path, exist_ok=True)
@@ -368,9 +376,9 @@ def run(dataset_dir: str, method: str, dataset: str, output: str = "output", len
     mine = paths[rank::world]
     t0 = time.perf_counter()
     per_case = []
-    if batch > 0 and method == "pc_pagerank":
+    if batch > 0 and method in batch_methods():
         per_case = _run_batched(mine, dataset, result_path, int(batch), prefetch, loader,
-                                dict(length=length, tdelta=tdelta, is_synthetic=is_synthetic))
+                                dict(length=length, tdelta=tdelta, is_synthetic=is_synthetic), method)
     elif prefetch > 0 and len(mine) > 1:
         # loaders (threads by default, or spawned processes) read and window the next cases while this
         # thread runs the current case on the GPU; cases are still processed, and their errors
@@ -428,7 +436,8 @@ def main(argv=None):
     ap.add_argument("--tdelta", type=int, default=0)
     ap.add_argument("--test", action="store_true")
     ap.add_argument("--batch", type=int, default=0,
-                    help="pc_pagerank: run the PC of up to this many cases in one batched launch (0 = per case)")
+                    help="pc_pagerank, baro, robust_scaler, nsigma: run up to this many cases in one batched launch "
+                         "(0 = per case)")
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))

@@ -700,6 +700,46 @@ int pcg_scaler_abi_info(int64_t *case_bytes);
 /* The largest N the in-LDS sort takes (host only).                                             */
 int pcg_scaler_limits(int64_t *lds_rows);
 
+/* ---- cMLP neural Granger training (cmlp, cmlp_pagerank) -------------------------------------
+ * Replaces `train_model_ista` (RCAEval/graph_construction/cmlp.py:478-540, penalty "H") for the
+ * model `cmlp()` builds (:591-618): p networks Conv1d(p, hidden, lag) -> ReLU -> Conv1d(hidden, 1,
+ * 1), full-batch ISTA in fp32 (sums over samples and groups accumulate in fp64). X: device T x p
+ * floats, row stride ldx (rows are time). params: device floats, in and out, the networks in
+ * order, per network W1[hidden][p][lag], b1[hidden], w2[hidden], b2[1] (torch's own layouts, so
+ * p * (hidden * p * lag + 2 * hidden + 1) floats); W1[h][c][k] multiplies X[t + k][c] in the
+ * prediction of X[t + lag][i]. Limits (pcg_cmlp_limits; anything else is PCG_ERR_INVALID before
+ * anything is launched): 1 <= hidden <= 128, 1 <= lag <= 8, 1 <= p <= 1024, ldx >= p, T < 2^24,
+ * lr > 0, lam >= 0, lam_ridge >= 0, all finite. T <= lag is PCG_ERR_DOMAIN. The handle keeps the
+ * lag-expanded data, two (T - lag) x hidden activations per network and, for pcg_cmlp_train, one
+ * copy of params.
+ *
+ * One iteration: the gradient of sum_i mse_i + lam_ridge * sum_i |w2_i|^2 at the current
+ * parameters, param <- param - lr * grad for every parameter, then (lam > 0) the hierarchical
+ * prox on W1: for k = 0..lag-1 in turn, per (network, input series c), with n = |W1[:, c, :k+1]|,
+ * W1[:, c, :k+1] <- W1[:, c, :k+1] / max(n, lr * lam) * max(n - lr * lam, 0). A group below the
+ * threshold becomes exactly 0. Two runs on the same input return bit-identical parameters.
+ *
+ * pcg_cmlp_train runs up to max_iter iterations. After iteration `it` with (it + 1) % check_every
+ * == 0 it takes mean_loss = (sum_i mse_i + lam_ridge * sum_i |w2_i|^2 + lam * sum_i sum_c sum_k
+ * |W1_i[:, c, :k+1]|) / p of the updated parameters and stores it in losses[check] (host out,
+ * max_iter / check_every doubles). A strictly smaller mean_loss snapshots params on the device
+ * and sets best_it = it; otherwise it - best_it == lookback * check_every ends the loop. On
+ * return params holds the best snapshot; n_checks, best_it, last_it (host out, any may be NULL):
+ * the checks taken, the best check's iteration and the last iteration run. PCG_ERR_DOMAIN where
+ * the reference raises: no check runs (max_iter < check_every), or the first check's loss is NaN
+ * or Inf (params is then left at that iterate). The iterations between two checks are queued
+ * without a host wait; each check reads one double. Synchronous on return.
+ *
+ * pcg_cmlp_steps runs k >= 0 iterations in place with no checks; smooth (host out, p doubles, may
+ * be NULL): the per-network MSEs of the returned parameters. Synchronous on return.            */
+int pcg_cmlp_train(pcg_handle *h, const float *X, int64_t T, int64_t p, int64_t ldx, int lag, int hidden,
+                   float *params, double lr, double lam, double lam_ridge, int64_t max_iter, int64_t check_every,
+                   int64_t lookback, double *losses, int64_t *n_checks, int64_t *best_it, int64_t *last_it);
+int pcg_cmlp_steps(pcg_handle *h, const float *X, int64_t T, int64_t p, int64_t ldx, int lag, int hidden,
+                   float *params, double lr, double lam, double lam_ridge, int64_t k, double *smooth);
+/* The limits the cMLP kernels were built with (host only, any may be NULL).                    */
+int pcg_cmlp_limits(int32_t *max_hidden, int32_t *max_lag, int32_t *max_p);
+
 #ifdef __cplusplus
 }
 #endif

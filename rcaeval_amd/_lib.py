@@ -204,6 +204,10 @@ SIGNATURES = [
     ("pcg_scaler_batch", I32, [P, ctypes.POINTER(PcgScalerCase), I64, ctypes.c_int, P, P, P, P]),
     ("pcg_scaler_abi_info", I32, [ctypes.POINTER(I64)]),
     ("pcg_scaler_limits", I32, [ctypes.POINTER(I64)]),
+    ("pcg_cmlp_train", I32, [P, P, I64, I64, I64, ctypes.c_int, ctypes.c_int, P, D, D, D, I64, I64, I64,
+                             ctypes.POINTER(D), ctypes.POINTER(I64), ctypes.POINTER(I64), ctypes.POINTER(I64)]),
+    ("pcg_cmlp_steps", I32, [P, P, I64, I64, I64, ctypes.c_int, ctypes.c_int, P, D, D, D, I64, ctypes.POINTER(D)]),
+    ("pcg_cmlp_limits", I32, [ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32)]),
 ]
 
 _lib = None

@@ -177,7 +177,8 @@ extern "C" int pcg_destroy(pcg_handle *h) {
                       &h->k1_digits, &h->small_sum, &h->batch_up, &h->batch_sum, &h->batch_near,
                       &h->granger_scratch, &h->granger_work, &h->lingam_w, &h->lingam_z, &h->lingam_d,
                       &h->lingam_small, &h->pcmci_e, &h->pcmci_r, &h->pcmci_small, &h->pcmci_work,
-                      &h->fges_e, &h->fges_r, &h->fges_small, &h->fges_list, &h->fges_work, &h->scaler_up};
+                      &h->fges_e, &h->fges_r, &h->fges_small, &h->fges_list, &h->fges_work, &h->scaler_up,
+                      &h->cmlp_scratch, &h->cmlp_best};
     for (DevBuf *b : bufs)
         if (b->p) hipFree(b->p);
     PinBuf *pins[] = {&h->ctr_pin, &h->deg_pin, &h->off_pin, &h->cpre_pin, &h->status_pin, &h->small_pin,

@@ -96,6 +96,9 @@ struct pcg_handle {
     bool fges_ok = false;
     DevBuf scaler_up;               // pcg_scaler_batch: the cases and the tile lists (one H2D copy)
     bool scaler_lds_set = false;    // k_sc_sort's dynamic-LDS limit was raised on this handle's device
+    // pcg_cmlp_*: the lag-expanded A, the forward pass's dZ / G / g and the loss partials; the best
+    // check's parameter snapshot
+    DevBuf cmlp_scratch, cmlp_best;
     DevBuf k1_digits;               // K1 int8 digit / residue planes of the centred X (corr.hip)
     // the (N, n, k, b) a CRT-mode pcg_corr_shard computed h->colmean's column exponents for;
     // pcg_corr_shard_finish refuses to rebuild C from exponents of any other call

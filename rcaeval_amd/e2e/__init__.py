@@ -47,7 +47,7 @@ def _dummy(args, kwargs):
 from .baro import baro, baro_batch, nsigma, nsigma_batch, robust_scaler  # noqa: E402
 from .circa import circa  # noqa: E402
 from .cloudranger import cloudranger  # noqa: E402
-from .pc_pagerank import pc_pagerank, pc_pagerank_batch  # noqa: E402
+from .pc_pagerank import cmlp_pagerank, pc_pagerank, pc_pagerank_batch  # noqa: E402
 from .fci_pagerank import fci_pagerank  # noqa: E402
 from .ges_pagerank import fges_pagerank, fges_randomwalk  # noqa: E402
 from .granger_pagerank import granger_pagerank  # noqa: E402
@@ -55,6 +55,6 @@ from .lingam_pagerank import micro_diag  # noqa: E402
 from .microcause import microcause  # noqa: E402
 from .pc_randomwalk import fci_randomwalk, granger_randomwalk, pc_randomwalk  # noqa: E402
 
-__all__ = ["rca", "baro", "baro_batch", "circa", "cloudranger", "fci_pagerank", "fci_randomwalk", "fges_pagerank",
+__all__ = ["rca", "baro", "baro_batch", "circa", "cloudranger", "cmlp_pagerank", "fci_pagerank", "fci_randomwalk", "fges_pagerank",
            "fges_randomwalk", "granger_pagerank", "granger_randomwalk", "micro_diag", "microcause", "nsigma",
            "nsigma_batch", "pc_pagerank", "pc_pagerank_batch", "pc_randomwalk", "robust_scaler"]

@@ -6,6 +6,10 @@ dropped, remaining nodes sorted (``:28``) -> dense matrix as networkx 2.5
 ``to_numpy_matrix`` (``:29``) -> GPU PageRank on its transpose (``:31-32``) -> scores zipped
 with the *unfiltered* ``node_names`` (``:33``: names and scores misalign, and the list is
 truncated, whenever a node is isolated — reproduced on purpose) -> stable descending sort.
+
+``cmlp_pagerank`` — mirror of ``:43-63``: preprocess -> ``cmlp(data, max_iter=20000)`` (the int
+Granger-causality matrix of the trained cMLP, ``graph_construction/cmlp.py``) -> GPU PageRank on
+its transpose -> scores zipped with ``node_names`` -> stable descending sort.
 """
 from __future__ import annotations
 
@@ -43,6 +47,21 @@ def pc_pagerank(data, inject_time=None, dataset=None, dk_select_useful=False, wi
     with phase("rank sort"):
         ranked = sorted(zip(node_names, scores), key=lambda t: t[1], reverse=True)
     return {"adj": M, "node_names": node_names, "ranks": [name for name, _ in ranked]}
+
+
+@rca
+def cmlp_pagerank(data, inject_time=None, dataset=None, dk_select_useful=False, with_bg=False, n_iter=10,
+                  **kwargs):
+    from ..graph_construction.cmlp import cmlp
+    with phase("preprocess"):
+        data = preprocess(data=data, dataset=dataset, dk_select_useful=dk_select_useful)
+        node_names = data.columns.to_list()
+    adj = cmlp(data, max_iter=20000)
+    with phase("pagerank"):
+        scores = PageRank().fit_transform(adj.T)
+    with phase("rank sort"):
+        ranked = sorted(zip(node_names, scores), key=lambda t: t[1], reverse=True)
+    return {"adj": adj, "node_names": node_names, "ranks": [name for name, _ in ranked]}
 
 
 def pc_pagerank_batch(cases, dataset=None, dk_select_useful=False, **kwargs) -> list:

@@ -598,6 +598,74 @@ class Engine:
         out["exact_items"] = int(exact.value)
         return out
 
+    # ------------------------------------------------------------------ cMLP
+    def _rows_f32(self, X):
+        """(device tensor, T, p, ldx) of a T x p input for the fp32 cMLP kernels: an fp32 tensor
+        already on this device whose rows are contiguous is used in place with its row stride,
+        anything else is cast (float64 -> float32, as the reference does) and uploaded."""
+        torch = _torch()
+        if not (isinstance(X, torch.Tensor) and X.device == self.device and X.dtype == torch.float32 and X.dim() == 2
+                and X.shape[1] >= 1 and X.stride(1) == 1 and X.stride(0) >= X.shape[1]):
+            if isinstance(X, torch.Tensor):
+                X = X.to(device=self.device, dtype=torch.float32).contiguous()
+            else:
+                X = torch.from_numpy(np.array(X, dtype=np.float32, order="C")).to(self.device)
+        if X.dim() != 2:
+            raise ValueError("expected a T x p array")
+        return X, int(X.shape[0]), int(X.shape[1]), int(X.stride(0)) if X.shape[0] > 1 else int(X.shape[1])
+
+    def _cmlp_params(self, params, p: int, lag: int, hidden: int):
+        """A private flat fp32 device copy of the packed parameters (the kernels update it in place)."""
+        torch = _torch()
+        if isinstance(params, torch.Tensor):
+            P = params.detach().to(device=self.device, dtype=torch.float32).reshape(-1).clone()
+        else:
+            P = torch.from_numpy(np.array(params, dtype=np.float32).reshape(-1)).to(self.device)
+        want = p * (hidden * p * lag + 2 * hidden + 1)
+        if P.numel() != want:
+            raise ValueError(f"cmlp: packed parameters hold {P.numel()} floats, p={p} lag={lag} hidden={hidden} needs {want}")
+        return P
+
+    def cmlp_limits(self) -> dict:
+        """The limits of the cMLP kernels (``pcg_cmlp_limits``)."""
+        from .graph_construction.cmlp import limits
+        return limits()
+
+    def cmlp_steps(self, X, params, k: int, lag: int = 5, hidden: int = 100, lr: float = 5e-2, lam: float = 0.002,
+                   lam_ridge: float = 1e-2) -> tuple:
+        """``k`` ISTA iterations of the cMLP on a T x p array with no checks (``pcg_cmlp_steps``).
+        ``params``: the packed parameters (``graph_construction.cmlp.pack``), host or device; a copy
+        is updated. Returns (packed fp32 device tensor, host float64 array of the p per-network
+        MSEs after the last step). ``T <= lag`` raises ``ValueError``."""
+        Xd, T, p, ldx = self._rows_f32(X)
+        P = self._cmlp_params(params, p, int(lag), int(hidden))
+        smooth = np.empty(p, dtype=np.float64)
+        check(self.h, self.lib.pcg_cmlp_steps(self.h, ctypes.c_void_p(Xd.data_ptr()), T, p, ldx, int(lag), int(hidden),
+                                              ctypes.c_void_p(P.data_ptr()), float(lr), float(lam), float(lam_ridge),
+                                              int(k), smooth.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+              "pcg_cmlp_steps")
+        return P, smooth
+
+    def cmlp_train(self, X, params, max_iter: int, lag: int = 5, hidden: int = 100, lr: float = 5e-2,
+                   lam: float = 0.002, lam_ridge: float = 1e-2, check_every: int = 1000, lookback: int = 5) -> dict:
+        """The cMLP's ISTA training loop with its early-stopping checks (``pcg_cmlp_train``) on a
+        T x p array. Returns ``params`` (packed fp32 device tensor: the best check's snapshot),
+        ``losses`` (host float64, one mean loss per check), ``n_checks``, ``best_it``, ``last_it``.
+        Raises ``ValueError`` where the reference raises: ``T <= lag``, ``max_iter < check_every``,
+        a first check whose loss is NaN or Inf."""
+        Xd, T, p, ldx = self._rows_f32(X)
+        P = self._cmlp_params(params, p, int(lag), int(hidden))
+        losses = np.zeros(max(1, int(max_iter) // max(1, int(check_every))), dtype=np.float64)
+        nc, bi, li = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        check(self.h, self.lib.pcg_cmlp_train(self.h, ctypes.c_void_p(Xd.data_ptr()), T, p, ldx, int(lag), int(hidden),
+                                              ctypes.c_void_p(P.data_ptr()), float(lr), float(lam), float(lam_ridge),
+                                              int(max_iter), int(check_every), int(lookback),
+                                              losses.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                              ctypes.byref(nc), ctypes.byref(bi), ctypes.byref(li)),
+              "pcg_cmlp_train")
+        return {"params": P, "losses": losses[:nc.value].copy(), "n_checks": int(nc.value), "best_it": int(bi.value),
+                "last_it": int(li.value)}
+
     def _rows(self, X):
         """(device tensor, T, n, ldx) of a T x n input: an fp64 tensor already on this device whose
         rows are contiguous is used in place with its row stride, anything else is uploaded."""

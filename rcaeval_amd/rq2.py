@@ -44,13 +44,13 @@ DATASET_MAP = {                                   # rq2.py:135-144
 
 def methods():
     """Methods this engine serves (``rq2.py:36-59`` resolves them by name)."""
-    from .e2e import (baro, circa, cloudranger, fges_pagerank, fges_randomwalk, granger_pagerank,
+    from .e2e import (baro, circa, cloudranger, cmlp_pagerank, fges_pagerank, fges_randomwalk, granger_pagerank,
                       granger_randomwalk, micro_diag, microcause, nsigma, pc_pagerank, pc_randomwalk, robust_scaler)
     return {"baro": baro, "robust_scaler": robust_scaler, "nsigma": nsigma,
             "pc_pagerank": pc_pagerank, "pc_randomwalk": pc_randomwalk, "cloudranger": cloudranger,
             "circa": circa, "granger_pagerank": granger_pagerank, "granger_randomwalk": granger_randomwalk,
             "micro_diag": micro_diag, "microcause": microcause, "fges_pagerank": fges_pagerank,
-            "fges_randomwalk": fges_randomwalk}
+            "fges_randomwalk": fges_randomwalk, "cmlp_pagerank": cmlp_pagerank}
 
 
 def dump_json(filename: str, data) -> None:
